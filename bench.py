@@ -21,6 +21,12 @@ Workloads (BASELINE.json configs):
 The ROM is the synthetic game `pkbench` (pokegym_amd/testrom/game.py; --rom-banks 64 for the
 Pokémon-Red-sized 1 MiB variant) because pokemon_red.gb is not shipped; --rom/--state run a real
 cartridge.  Inputs are resident in HBM before the timed region (actions pre-generated on device).
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds the legs that
+take runs of their own: the C oracle's CPU baseline (`cpu_baseline`, ~20 s of host time; config1:
+its one-process CPU reference point).  --dump-outputs DIR writes what the last timed step handed
+its caller (obs of a fixed sample of envs, every env's reward / terminal / truncation) as
+DIR/<name>.npy after the timed region; the same arguments give the same inputs and outputs.
 """
 from __future__ import annotations
 
@@ -174,6 +180,55 @@ def _stamp(workload: str, rom_tag: str):
     return d, os.path.relpath(path, HERE)
 
 
+DUMP_SAMPLE_ENVS = 512   # envs whose obs is dumped: 512 x 23,040 B as float32 = 47 MB (the limit is 64 MB in all)
+
+
+def _save_outputs(path: str, arrays: dict, rank: int = 0, world: int = 1):
+    """DIR/<name>.npy (float32 / float64); with several ranks every rank writes its shard as
+    <name>_rank<r>.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    tag = f"_rank{rank}" if world > 1 else ""
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, f"{name}{tag}.npy"), a)
+
+
+def _last_outputs(emu, vec, dev) -> dict:
+    """What the last env-step handed its caller, after the timed region: VecEnv workloads — each
+    sub-batch's (obs, rewards, terminals, truncations) that the next recv() returns (finished envs
+    already auto-reset: their obs is the next episode's first); otherwise emu.step's return values.
+    Rewards / terminals / truncations of every env; the obs (headless config2: the 8 KiB WRAM, its
+    RAM-only obs) of a fixed, seeded sample of DUMP_SAMPLE_ENVS envs, listed in `obs_envs`."""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize(dev)
+    if vec is None:
+        n = emu.n
+        rew, term, trunc = emu.rewards, emu.terminals, emu.truncations
+    else:
+        n = vec.num_envs
+        if vec.num_batches == 1:
+            _, rew, term, trunc, _ = vec._pending
+        else:
+            rew, term, trunc = (torch.cat([p[i] for p in vec._pending]) for i in range(3))
+    envs = np.sort(np.random.default_rng(0).choice(n, size=min(n, DUMP_SAMPLE_ENVS), replace=False))
+    phys = torch.as_tensor([vec.phys(int(e)) for e in envs] if vec is not None else envs, device=dev)
+    out = {
+        "obs_envs": envs.astype(np.float64),
+        "rewards": rew.to(torch.float64).cpu().numpy(),
+        "terminals": term.to(torch.float32).cpu().numpy(),
+        "truncations": trunc.to(torch.float32).cpu().numpy(),
+    }
+    if emu.render:
+        obs = emu.obs if emu.reward else emu.screen
+        out["obs"] = obs.index_select(0, phys).to(torch.float32).cpu().numpy()
+    else:
+        out["ram"] = emu.get_ram(0xC000, 0x2000).index_select(0, phys).to(torch.float32).cpu().numpy()
+    return out
+
+
 class StepFlow:
     """One env-step of the benchmarked workload over every env of this rank (the timed unit).
 
@@ -220,17 +275,19 @@ def run_config1(args):
         g.power_on()
         state = g.save_state()
         del g
-    # CPU reference point first (no GPU touched yet): one process, emulation only
-    g = oracle.GB(rom, state)
-    cw = min(args.warmup, 1000)
-    for _ in range(cw):
-        g.run_action(0)
-    cs = min(args.steps, 5000)
-    t0 = time.perf_counter()
-    for _ in range(cs):
-        g.run_action(0)
-    cpu_rate = cs / (time.perf_counter() - t0)
-    del g
+    # --full: CPU reference point first (no GPU touched yet): one process, emulation only
+    cpu_rate = None
+    if args.full:
+        g = oracle.GB(rom, state)
+        cw = min(args.warmup, 1000)
+        for _ in range(cw):
+            g.run_action(0)
+        cs = min(args.steps, 5000)
+        t0 = time.perf_counter()
+        for _ in range(cs):
+            g.run_action(0)
+        cpu_rate = cs / (time.perf_counter() - t0)
+        del g
 
     env = Environment(rom_path=rom, state_path=state)
     env.reset()
@@ -240,9 +297,10 @@ def run_config1(args):
             print(f"config1 warm-up {i + 1}/{args.warmup}", file=sys.stderr, flush=True)
     torch.cuda.synchronize()
     env.emu.profile_enable(True)
+    last = None
     t0 = time.perf_counter()
     for i in range(args.steps):
-        env.step(0)
+        last = env.step(0)
         if (i + 1) % 500 == 0:
             print(f"config1 step {i + 1}/{args.steps}", file=sys.stderr, flush=True)
     torch.cuda.synchronize()
@@ -250,6 +308,11 @@ def run_config1(args):
     emu_ms, ren_ms, rew_ms, nprof = env.emu.profile_read()
     instr = env.emu.last_instr_count()
     env.close()
+    if args.dump_outputs and last is not None:   # the last step(0)'s (obs, reward, terminated, truncated)
+        import numpy as np
+        _save_outputs(args.dump_outputs, {"obs": last[0].astype(np.float32), "rewards": np.array([last[1]], np.float64),
+                                          "terminals": np.array([last[2]], np.float32),
+                                          "truncations": np.array([last[3]], np.float32)})
     k = max(nprof, 1)
     span = (emu_ms + ren_ms + rew_ms) / k
     out = {
@@ -273,13 +336,14 @@ def run_config1(args):
                        "k2_render": round(ren_ms / k, 3), "k4_k3_reward_obs": round(rew_ms / k, 3),
                        "host_and_launch": round(elapsed / args.steps * 1e3 - span, 3)},
         "instr_per_env_step": instr,
-        "cpu_baseline": {"value": round(cpu_rate, 2), "unit": "env-steps/s", "cores": 1, "kind": "port",
-                         "sample": (f"C oracle (oracle/gbcore.c) in this process, one env, {cw} x step(0) warm-up then "
-                                    f"{cs} x step(0) timed; emulation only (no reward stack, no obs)")},
         "note": ("one env leaves 1 of the GPU's 65,536 lanes busy: each emulated instruction is a dependent chain "
                  "of LDS and memory round trips with nothing to hide them, so this shape measures latency, not "
                  "throughput (use VecEnv)"),
     }
+    if cpu_rate is not None:
+        out["cpu_baseline"] = {"value": round(cpu_rate, 2), "unit": "env-steps/s", "cores": 1, "kind": "port",
+                               "sample": (f"C oracle (oracle/gbcore.c) in this process, one env, {cw} x step(0) warm-up then "
+                                          f"{cs} x step(0) timed; emulation only (no reward stack, no obs)")}
     print(json.dumps(out), flush=True)
 
 
@@ -303,7 +367,14 @@ def main():
     ap.add_argument("--rom", default=None)
     ap.add_argument("--rom-banks", type=int, default=4, help="pkbench size in 16 KiB banks (4, or 64 = 1 MiB)")
     ap.add_argument("--state", default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own: the C oracle's CPU baseline "
+                         "(`cpu_baseline` in the line; off by default, a plain run only times its steps)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as "
+                         "DIR/<name>.npy (float32/float64: rewards, terminals, truncations of every env; obs of a "
+                         "fixed sample of envs, listed in obs_envs)")
     ap.add_argument("--host-obs", action="store_true",
                     help="diagnostic: also hand every step's observation to the host (pinned buffers, D2H on a "
                          "copy stream overlapped with the next step) inside the timed region -- the PCIe-inclusive "
@@ -447,6 +518,8 @@ def main():
     if world > 1:
         dist.all_reduce(t_max, op=dist.ReduceOp.MAX)
     elapsed = float(t_max.item())
+    if args.dump_outputs:
+        _save_outputs(args.dump_outputs, _last_outputs(emu, vec, dev), rank, world)
 
     if rank == 0:
         value = world * n * args.steps / elapsed
@@ -565,7 +638,7 @@ def main():
             "episodes_logged": [round(d.get("episodes", 0.0)) for d in timed_logs] if vec is not None else None,
             "note": None if world > 1 else "one rank: the all-reduce is an identity and is not issued",
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 out["cpu_baseline"] = _cpu_baseline(rom, state)
             except Exception as e:  # noqa: BLE001

@@ -5,7 +5,8 @@ CPU: every committed PMC stamp (profiles/pmc_<workload>.json, what a bench line 
 rocprofv3 kernel-stats file it names as its source exists in the repo and agrees with the stamp's
 K1 average.  GPU: one short `python bench.py` run prints ONE JSON line with the driver's keys, a
 `roofline` object whose achieved/peak/frac are consistent, and a `value` that is the env-steps of
-the timed steps over the timed span."""
+the timed steps over the timed span; its `--dump-outputs` files are the last timed step's outputs
+as float32 / float64 arrays, and a plain run (no `--full`) carries no CPU baseline."""
 import csv
 import json
 import os
@@ -55,14 +56,45 @@ def test_cpu_quota_parses():
     assert cores is None or cores >= 1
 
 
+def test_save_outputs_names_and_dtypes(tmp_path):
+    import numpy as np
+    import bench
+    arrays = {"obs": np.arange(6, dtype=np.float32).reshape(2, 3), "rewards": np.array([0.5, -1.0])}
+    bench._save_outputs(str(tmp_path / "d"), arrays)
+    bench._save_outputs(str(tmp_path / "d"), arrays, rank=1, world=2)
+    assert sorted(os.listdir(tmp_path / "d")) == ["obs.npy", "obs_rank1.npy", "rewards.npy", "rewards_rank1.npy"]
+    for name, a in arrays.items():
+        got = np.load(tmp_path / "d" / f"{name}.npy")
+        assert got.dtype == a.dtype and np.array_equal(got, a)
+    with pytest.raises(AssertionError):   # float32 / float64 only
+        bench._save_outputs(str(tmp_path / "e"), {"terminals": np.zeros(2, np.uint8)})
+
+
 @pytest.mark.gpu
-def test_bench_line_contract():
+def test_bench_line_contract(tmp_path):
+    import numpy as np
+    dump = tmp_path / "outputs"
     out = subprocess.run([sys.executable, os.path.join(HERE, "bench.py"), "--steps", "3", "--warmup", "1",
-                          "--no-cpu-baseline"], capture_output=True, text=True, timeout=240, cwd=HERE)
+                          "--no-cpu-baseline", "--dump-outputs", str(dump)],
+                         capture_output=True, text=True, timeout=240, cwd=HERE)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip().startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
     d = json.loads(lines[0])
+    assert "cpu_baseline" not in d          # a plain run: the CPU baseline is a --full leg
+    # --dump-outputs: the last timed step's outputs, float32 / float64 .npy files, 64 MB at the most
+    got = {f[:-4]: np.load(dump / f) for f in sorted(os.listdir(dump))}
+    assert sorted(got) == ["obs", "obs_envs", "rewards", "terminals", "truncations"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(os.path.getsize(dump / f) for f in os.listdir(dump)) <= 64 * 2**20
+    n = d["config"]["envs_per_gpu"]
+    assert got["rewards"].shape == got["terminals"].shape == got["truncations"].shape == (n,)
+    k = len(got["obs_envs"])
+    assert got["obs"].shape == (k, 144, 160) and 0 < k <= n
+    assert np.all(np.diff(got["obs_envs"]) > 0) and 0 <= got["obs_envs"][0] and got["obs_envs"][-1] < n
+    # a screen of the four DMG greys (smoke()'s palette), not an empty buffer
+    assert set(np.unique(got["obs"])) <= {0.0, 85.0, 153.0, 255.0} and len(np.unique(got["obs"])) > 1
+    assert not got["terminals"].any()       # 4 env-steps into 20,480-step episodes
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline"):
         assert k in d, k

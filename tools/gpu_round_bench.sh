@@ -1,5 +1,5 @@
 #!/bin/bash
-# Round-final bench lines: the driver's default command (config3 with the CPU baseline), every
+# Round-final bench lines: the default workload with the CPU baseline (config3, --full), every
 # workload without it, the 64-bank ROM, and throughput vs envs per GPU (configs[3] shard sizes of
 # N = 8, 4, 2, 1).  Each GPU step has its own time limit; the chain stops at the first failure.
 # usage: bash tools/gpu_round_bench.sh TAG   (outputs in gpurun_out/rbench_TAG)
@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/rbench_${1:-x}
 mkdir -p $OUT
 cd $R
 B="timeout -k 10 400 python bench.py"
-$B > $OUT/default.json 2> $OUT/err.log && \
+$B --full > $OUT/default.json 2> $OUT/err.log && \
 $B --no-cpu-baseline --workload config2 > $OUT/config2.json 2>> $OUT/err.log && \
 $B --no-cpu-baseline --workload config4 > $OUT/config4.json 2>> $OUT/err.log && \
 $B --no-cpu-baseline --workload config5 > $OUT/config5.json 2>> $OUT/err.log && \

@@ -23,7 +23,7 @@ mkdir -p $OUT
 if [ "$1" = prof ]; then
   cd /tmp && export TMPDIR=/tmp
   timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/stats -o stats --output-format csv -- \
-      python3 $R/bench.py > $OUT/driver_cmd_bench_under_rocprof.json 2> $OUT/driver_cmd.err && \
+      python3 $R/bench.py --full > $OUT/driver_cmd_bench_under_rocprof.json 2> $OUT/driver_cmd.err && \
   bash $R/tools/gpu_round_prof.sh $TAG "config3|--workload config3" "config4|--workload config4" \
       "config5|--workload config5"
 elif [ "$1" = prof2 ]; then
@@ -36,7 +36,7 @@ elif [ "$1" = stamp ]; then
       "config4|--workload config4" "config2|--workload config2"
 else
   bash $R/tools/gpu_round_bench.sh $TAG && \
-  cd $R && timeout -k 10 900 python bench.py --workload config1 > $OUT/config1_full.json 2> $OUT/config1.err
+  cd $R && timeout -k 10 900 python bench.py --full --workload config1 > $OUT/config1_full.json 2> $OUT/config1.err
 fi
 rc=$?
 echo "exit=$rc" > $OUT/exit_$1.txt
