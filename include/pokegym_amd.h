@@ -73,7 +73,15 @@ typedef struct pk_config {
     const uint8_t* state;        /* host bytes of a PyBoy v9 savestate, or NULL = power-on */
     uint64_t state_len;
     uint32_t frame_skip;         /* frames per env-step; pokegym uses 24 (pyboy_binding.py:72) */
-    uint32_t release_frame;      /* button released before this frame; pokegym: 8 (:80) */
+    uint32_t release_frame;      /* button released before this frame; pokegym: 8 (:80).
+                                    0 = pressed and released before the step's first frame.
+                                    release_frame >= frame_skip: that frame is not part of the
+                                    step, so the step releases nothing (the reference's loop
+                                    never reaches i == release_frame, :79-81): the button stays
+                                    down across the step's end and the next step presses its own
+                                    button on top of it.  As both values are fixed per handle,
+                                    a button once pressed is then held until the env's state is
+                                    reloaded (reset, pk_load_env) */
     uint32_t flags;              /* PK_F_* */
     uint32_t max_episode_steps;  /* truncation horizon; pokegym default 20480 (environment.py:1233) */
     double reward_scale;         /* reset(reward_scale=4.0) (environment.py:1233); 0 = 4.0 */

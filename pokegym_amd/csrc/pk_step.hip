@@ -973,6 +973,15 @@ static __device__ void pk_check_lane(const St& s, const Ctx& c, int slack, u32 p
             PK_CHECK(env, e.x == q[k].x && e.y == q[k].y && e.z == q[k].z && e.w == q[k].w, "prefetched microcode stale");
         }
     }
+    // flush_lines reads only the latch flags of npend's range (pk_render.h): a pending flag outside
+    // it would never be rasterised by a flush, and prow is the rows of that range's lines only
+    const u32 ylo = s.npend >> 16, yend = s.npend & 0xFFFFu;
+    PK_CHECK(env, yend <= PK_ROWS && (s.npend == 0u || ylo < yend), "npend is not a line range");
+    for (u32 y = 0; y < PK_ROWS; y++) {
+        const u32 l2 = c.A->lat[2u * c.A->lat_stride + (c.gid * PK_ROWS + y) * PK_LANES + c.glane];
+        PK_CHECK(env, !(l2 & 0x100u) || (y >= ylo && y < yend), "pending latch flag outside npend's range");
+    }
+    PK_CHECK(env, s.npend != 0u || s.prow == 0u, "prow != 0 with no pending line");
 }
 #endif
 
@@ -1071,7 +1080,11 @@ __global__ void __launch_bounds__(PK_K1_MAX_THREADS) PK_K1_KERNEL(PkStepArgs A) 
     const u32 btn = action == 0u ? 3u : action == 1u ? 1u : action == 2u ? 0u : action == 3u ? 2u
                   : action == 4u ? 4u : action == 5u ? 5u : action == 6u ? 7u : action == 7u ? 6u : 0xFFu;
     if (active && btn != 0xFFu) key_event(s, btn, true);
-    if (active && A.frames > 0u && A.release_frame == 0u && btn != 0xFFu) key_event(s, btn, false);
+    // the reference releases at the top of loop pass i == release_frame (pyboy_binding.py:79-81): a
+    // pass that does not exist (release_frame >= frame_skip) releases nothing, and the button stays
+    // down into the next step
+    const u32 release = A.release_frame < A.frames ? A.release_frame : ~0u;
+    if (active && release == 0u && btn != 0xFFu) key_event(s, btn, false);
     // (no latch flags to clear for the rendered frame: every consumer of a latched line — K2,
     // flush_lines, K2's blank-screen path — clears its flag)
     s.render = (A.render_last && frame + 1u == A.frames) ? 1u : 0u;
@@ -1491,7 +1504,7 @@ __global__ void __launch_bounds__(PK_K1_MAX_THREADS) PK_K1_KERNEL(PkStepArgs A) 
                 s.frame_done = 0;
                 slack = (int)(16u * FRAME_CYCLES);
                 frame += 1u;
-                if (frame == A.release_frame && btn != 0xFFu) key_event(s, btn, false);
+                if (frame == release && btn != 0xFFu) key_event(s, btn, false);
                 s.render = (A.render_last && frame + 1u == A.frames) ? 1u : 0u;
             }
             s.lim = tick_lim(s, slack);

@@ -37,7 +37,8 @@ def lib():
 
 
 class SimEmulator:
-    def __init__(self, rom: bytes, n: int, state: bytes | None = None, render: bool = True):
+    def __init__(self, rom: bytes, n: int, state: bytes | None = None, render: bool = True,
+                 frame_skip: int = 24, release_frame: int = 8):
         L = lib()
         self._rom = np.frombuffer(rom, np.uint8).copy()
         cfg = PkConfig()
@@ -48,7 +49,7 @@ class SimEmulator:
             self._st = np.frombuffer(state, np.uint8).copy()
             cfg.state = self._st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
             cfg.state_len = len(self._st)
-        cfg.frame_skip, cfg.release_frame, cfg.flags, cfg.max_episode_steps = 24, 8, 1 if render else 0, 20480
+        cfg.frame_skip, cfg.release_frame, cfg.flags, cfg.max_episode_steps = frame_skip, release_frame, 1 if render else 0, 20480
         h = ctypes.c_void_p()
         rc = L.pk_create(ctypes.byref(cfg), ctypes.byref(h))
         if rc:

@@ -388,3 +388,105 @@ def test_sm83_kat_on_device(small, monkeypatch):
     ref, _ = oracle.batch_run(rom, None, np.repeat(acts[None, :], steps, axis=0), want_screens=False)
     bad = [e for e in range(n) if states[e].tobytes() != ref[e].tobytes()]
     assert not bad, bad[:8]
+
+
+# ---------------------------------------------------------------------------------------------
+# Every step end, not only the last: per-frame parity (frame_skip=1) and the other values of
+# frame_skip / release_frame, the two pk_config fields the tests above never vary.
+def _lockstep(rom, state, acts, frame_skip, release_frame, tally=None):
+    """BatchedEmulator and n oracle emulators stepped side by side over acts (steps, n): the whole
+    v9 state of every env and its screen compared after EVERY step; returns the mismatches
+    [(step, env, first differing bytes)] of the first step that has one."""
+    import torch
+    from pokegym_amd.emulator import BatchedEmulator
+    from tests.test_frame_boundary import GREY, OracleBatch
+    steps, n = acts.shape
+    emu = BatchedEmulator(rom, n, state=state, render=True, frame_skip=frame_skip, release_frame=release_frame)
+    ob = OracleBatch(rom, n, state)
+    bad = []
+    for t in range(steps):
+        emu.step(torch.from_numpy(acts[t]).to(emu.device))
+        ref, ref_scr = ob.step(acts[t], frame_skip, release_frame)
+        gpu = emu.snapshot_range(0, n)              # synchronous
+        scr = emu.screen.cpu().numpy()
+        if tally is not None:
+            tally.add(gpu, t)
+        if not np.array_equal(gpu, ref) or not np.array_equal(scr, GREY[ref_scr]):
+            bad = [(t, e, _diff(gpu[e].tobytes(), ref[e].tobytes())) for e in range(n)
+                   if not np.array_equal(gpu[e], ref[e]) or not np.array_equal(scr[e], GREY[ref_scr[e]])]
+            break
+    emu.close()
+    ob.close()
+    return bad
+
+
+# frames per case: 72 (144 for the warp fixture), halved where the case ran longer than
+# test_vram_midframe_parity (1.5-1.6 s) in the same MI355X run — vram_midframe took 6.5 s at 72
+# frames (every frame is rendered, so each of its ~10 mid-frame writes per frame flushes the pending
+# lines inside K1, lane by lane), the warp fixture 1.6 s at 144 and fuzz3 1.6 s at 72.  vram_midframe
+# cannot be halved again: its 3 LCD-off boot frames would be more than 10 % of 18.  The warp
+# fixture's first 72 frames hold the recorded door warp (LCD off in frames 57-61) and ten rendered
+# frames after it.
+PER_FRAME_STEPS = {"pkbench": 72, "fuzz3": 36, "vram_midframe": 36, "warp": 72}
+_per_frame_tallies = {}
+
+
+def _per_frame(name, small):
+    """One per-frame case (cached: the coverage test below reads the tallies of the cases run)."""
+    from tests.test_frame_boundary import FrameEndTally, frame_case
+    if (name, small) not in _per_frame_tallies:
+        rom, state, acts, mult4 = frame_case(name, 96, PER_FRAME_STEPS[name])
+        tally = FrameEndTally()
+        bad = _lockstep(rom, state, acts, 1, 8, tally)
+        _per_frame_tallies[(name, small)] = (tally, bad, mult4)
+    return _per_frame_tallies[(name, small)]
+
+
+@pytest.mark.parametrize("small", [False, True])
+@pytest.mark.parametrize("name", ["pkbench", "fuzz3", "vram_midframe", "warp"])
+def test_per_frame_parity(name, small, monkeypatch):
+    """frame_skip=1, release_frame=8: every frame is a step end and is rasterised (K1 enters with
+    s.render set; the pend_hit / flush_lines filter and K2 run on every frame).  96 envs — one full
+    64-env group and a ragged half — of pkbench, fuzz_rom(3), vram_midframe_rom and the warp fixture
+    (test_map_load_warp_parity's action layout with each action held 24 frames, so the LCD-off
+    frames of the map load are rendered and compared), PER_FRAME_STEPS frames; whole v9 state and
+    screen vs the oracle after every frame, in the default kernel and in the small-LDS kernel; every
+    snapshot satisfies PyBoy's frame-end facts (tests/test_frame_boundary.py check_frame_end), at
+    most 10 % of them without evidence (LCD off / off VBlank)."""
+    if small:
+        monkeypatch.setenv("PK_K1_SMALL", "1")
+        monkeypatch.setenv("PK_WAVE_LANES", "32")
+        monkeypatch.setenv("PK_K1_BLOCK", "256")
+    tally, bad, mult4 = _per_frame(name, small)
+    print(name, "small" if small else "default", tally.report())
+    assert not bad, bad[:4]
+    tally.assert_ok(mult4)
+
+
+def test_per_frame_parity_covers_halted_and_overshooting_ends():
+    """Across the ROM list (default kernel) halted frame ends and running ones whose last
+    instruction ran past the boundary were both checked on the device."""
+    tallies = [_per_frame(name, False)[0] for name in PER_FRAME_STEPS]
+    assert sum(t.halted for t in tallies) > 0
+    assert sum(c for t in tallies for o, c in t.overshoot.items() if o > 0) > 0
+
+
+@pytest.mark.parametrize("name", ["pkbench", "irq_bank"])
+@pytest.mark.parametrize("frame_skip,release_frame", [(1, 0), (2, 1), (8, 8), (9, 8), (24, 0), (24, 23), (24, 24),
+                                                      (8, 200)])
+def test_frame_skip_release_frame_parity(frame_skip, release_frame, name):
+    """pk_config's frame_skip and release_frame away from 24 / 8, on pkbench and irq_bank_rom(8) (its
+    joypad-interrupt traffic), 96 envs, actions 0..8 (some envs press nothing), whole v9 state and
+    screen vs the oracle after every step.  The reference releases the button at the top of loop
+    pass i == release_frame (pyboy_binding.py:79-81); with release_frame >= frame_skip — (8,8),
+    (24,24), (8,200) — that pass does not exist, the step releases nothing and the button is still
+    down when the next step presses."""
+    from pokegym_amd.testrom.fuzz import irq_bank_rom
+    from pokegym_amd.testrom.game import game_rom
+    rom = game_rom() if name == "pkbench" else irq_bank_rom(8)
+    n, steps = 96, 24 if frame_skip <= 2 else 6
+    if name == "irq_bank" and frame_skip == 24 and release_frame >= 23:
+        steps = 3   # 2.7 s at 6 steps (the button held through the whole step), longer than test_vram_midframe_parity
+    acts = np.random.default_rng(1000 * frame_skip + release_frame).integers(0, 9, size=(steps, n), dtype=np.uint8)
+    bad = _lockstep(rom, None, acts, frame_skip, release_frame)
+    assert not bad, bad[:4]
