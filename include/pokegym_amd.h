@@ -23,6 +23,12 @@
  *   pk_error_ptr     exceptions the reference raises   environment.py:739,744,568/580,1519,676
  *   pk_get_ram       per-env RAM views (RAM-only obs)  ram_map.py:1768-1770 (batched)
  *   pk_set_ram       per-env RAM writes                ram_map.py:1772-1774 (batched)
+ *   pk_bank_put      the pool of start states          environment.py:51, :116 (get_random_state),
+ *                                                      :122 (initial_states)
+ *   pk_bank_save     save_state, kept on the device    environment.py:208-214
+ *   pk_bank_load     load_first/last/random_state,     environment.py:219-227, :215-217
+ *                    load_pokemon_center_state
+ *   pk_reset_from    reset from a state of the pool    environment.py:116, :122, :1241-1242
  * With PK_F_REWARD, pk_step also runs the reward stack of Environment.step
  * (environment.py:1338-1612) and pk_reset follows Environment.reset (:1233-1334).
  */
@@ -35,7 +41,7 @@
 extern "C" {
 #endif
 
-#define PK_ABI_VERSION 6
+#define PK_ABI_VERSION 7
 #define PK_STATE_V9_BYTES 142610u
 #define PK_SCREEN_ROWS 144u
 #define PK_SCREEN_COLS 160u
@@ -169,6 +175,57 @@ int pk_load_env(pk_handle* h, uint32_t env, const uint8_t* host_v9, uint64_t len
 /* v9 savestates of envs [env0, env0 + count) into host_v9 (count * PK_STATE_V9_BYTES bytes,
  * env-major): the bulk form of pk_snapshot for whole-batch parity checks (synchronous) */
 int pk_snapshot_range(pk_handle* h, uint32_t env0, uint32_t count, uint8_t* host_v9, uint64_t len);
+
+/* Savestate bank: n_slots slots of machine state in device memory, for starting episodes from a
+ * pool of savestates and for copying one env's state over another's without the host — the
+ * batched form of the reference's state hooks (environment.py get_random_state :51, :116;
+ * initial_states with load_first_state / load_last_state / load_random_state :122, :219-227;
+ * save_state / load_pokemon_center_state :208-217).
+ *
+ * A slot holds what a parsed v9 savestate holds: the dense RAM image, the machine registers, the
+ * 3 x 144 scanline latches and the 144 x 160 screen, about 74.5 KB.  The step counter and the
+ * per-step bookkeeping registers are not machine state; a slot stores them as a freshly parsed
+ * state has them (0).  The reward stack's bookkeeping (seen-coordinate sets, heat maps, the
+ * per-episode attributes) is NOT in a slot: a load leaves it as it is, a reset rebuilds it.
+ *
+ * pk_bank_create (synchronous): once per handle, before any other bank call; n_slots in
+ * 1..65536.  On failure (second call, bad n_slots, out of memory) the handle stays usable and
+ * has no bank.  pk_destroy frees the bank.  pk_bank_slots: the slot count, 0 without a bank.
+ * Every other bank call on a handle without a bank fails with a negative code. */
+int pk_bank_create(pk_handle* h, uint32_t n_slots);
+uint32_t pk_bank_slots(const pk_handle* h);
+/* Synchronous, host v9 bytes: put parses a savestate into a slot (as pk_create parses the
+ * template) and marks it filled; get exports a filled slot exactly as pk_snapshot exports an env
+ * (an empty slot fails).  The pool-from-files path and the parity path. */
+int pk_bank_put(pk_handle* h, uint32_t slot, const uint8_t* host_v9, uint64_t len);
+int pk_bank_get(pk_handle* h, uint32_t slot, uint8_t* host_v9, uint64_t len);
+/* Stream-ordered, asynchronous, never a host sync.  slot_of_env_dev is a device i32[n], full
+ * size and indexed by env like every array of the range forms; only [env0, env0 + count) is
+ * read, env0 a multiple of 64 (pk_step_range's rule).  A negative slot: the env takes no part.
+ * Disjoint ranges may run concurrently on different streams (the bank keeps its own lists per
+ * range); the caller orders calls that touch the same slot.
+ *   pk_bank_save   slot[slot_of_env[e]] <- env e, and marks the slot filled: pk_bank_get of the
+ *                  slot then returns the bytes pk_snapshot(e) returned at that point of the stream.
+ *                  Two envs naming one slot in one call is a caller error: the slot then holds an
+ *                  unspecified mixture of the two.
+ *   pk_bank_load   env e <- slot[slot_of_env[e]], with pk_load_env's semantics: the RAM image,
+ *                  the machine registers, latches and screen; the env's step counter, per-step
+ *                  bookkeeping and all reward-stack state survive.
+ * A slot >= n_slots, or (load) an empty slot, never faults: that env is left untouched and the
+ * bank's reject counter is incremented. */
+int pk_bank_save(pk_handle* h, const int32_t* slot_of_env_dev, uint32_t env0, uint32_t count, void* stream);
+int pk_bank_load(pk_handle* h, const int32_t* slot_of_env_dev, uint32_t env0, uint32_t count, void* stream);
+/* pk_reset_range, except that an env that reloads its template reloads slot[slot_of_env[e]]
+ * instead; a negative slot is the handle's own template.  Without PK_F_REWARD every masked env
+ * reloads; with it the reload follows pk_reset's rule (the env's first reset only, or every
+ * reset with PK_F_RELOAD_ON_RESET), between the same steps of Environment.reset.  An env whose
+ * slot is >= n_slots or empty reloads the handle's template and is counted as a reject.
+ * slot_of_env_dev == NULL is exactly pk_reset_range. */
+int pk_reset_from(pk_handle* h, uint32_t env0, uint32_t count, const uint8_t* env_mask_dev,
+                  const int32_t* slot_of_env_dev, void* stream);
+/* Envs rejected by pk_bank_save / pk_bank_load / pk_reset_from since the last call; clears the
+ * counter (synchronous). */
+int pk_bank_rejects(pk_handle* h, uint64_t* out);
 
 /* Emulated instructions executed by the last pk_step, summed over envs (synchronous). */
 int pk_last_instr_count(pk_handle* h, uint64_t* out);

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # PK_LIB selects an alternative in-tree build (A/B kernel experiments); default: lib/libpokegym_amd.so
 LIB_PATH = os.environ.get("PK_LIB") or os.path.join(HERE, "lib", "libpokegym_amd.so")
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 PK_F_RENDER = 1
 PK_F_REWARD = 2
 PK_F_RELOAD_ON_RESET = 4
@@ -31,7 +31,9 @@ EXPORTS = ("pk_create", "pk_destroy", "pk_last_error", "pk_abi_version", "pk_res
            "pk_last_instr_count", "pk_profile_enable", "pk_profile_read", "pk_obs_ptr", "pk_error_ptr",
            "pk_get_ram", "pk_set_ram", "pk_info_ptr", "pk_info_flag_ptr", "pk_info_stride", "pk_heatmap_ptr", "pk_info_bits_ptr",
            "pk_snapshot_range", "pk_render_latched", "pk_step_range", "pk_reset_range",
-           "pk_set_episode_params", "pk_launch_shape")
+           "pk_set_episode_params", "pk_launch_shape",
+           "pk_bank_create", "pk_bank_slots", "pk_bank_put", "pk_bank_get", "pk_bank_save", "pk_bank_load",
+           "pk_reset_from", "pk_bank_rejects")
 
 
 class PkConfig(ctypes.Structure):
@@ -98,6 +100,7 @@ def bind(L):
     dp = ctypes.POINTER(ctypes.c_double)
     L.pk_profile_read.argtypes = [vp, dp, dp, dp, ctypes.POINTER(ctypes.c_uint64)]
     bind_v2(L)
+    bind_v7(L)
 
 
 def bind_v2(L):
@@ -123,6 +126,22 @@ def bind_v2(L):
     L.pk_step_range.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, vp, vp]
     L.pk_reset_range.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
     L.pk_set_episode_params.argtypes = [vp, ctypes.c_uint32, ctypes.c_double]
+
+
+def bind_v7(L):
+    """argtypes of the savestate bank (ABI v7; shared with the host-simulation test build)."""
+    vp = ctypes.c_void_p
+    u32 = ctypes.c_uint32
+    u8p = ctypes.POINTER(ctypes.c_uint8)
+    L.pk_bank_create.argtypes = [vp, u32]
+    L.pk_bank_slots.argtypes = [vp]
+    L.pk_bank_slots.restype = u32
+    L.pk_bank_put.argtypes = [vp, u32, u8p, ctypes.c_uint64]
+    L.pk_bank_get.argtypes = [vp, u32, u8p, ctypes.c_uint64]
+    L.pk_bank_save.argtypes = [vp, vp, u32, u32, vp]
+    L.pk_bank_load.argtypes = [vp, vp, u32, u32, vp]
+    L.pk_reset_from.argtypes = [vp, u32, u32, vp, vp, vp]
+    L.pk_bank_rejects.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
 
 
 def check(rc: int, what: str):

@@ -39,6 +39,8 @@ hipError_t pk_launch_seen_rehash(const uint32_t* old_tab, uint32_t old_lg, uint3
                                  const uint32_t* rs, uint32_t n, uint32_t np, hipStream_t s);
 hipError_t pk_launch_ram_copy(uint8_t* mem, uint8_t* dense, uint32_t n, uint32_t sh, uint32_t phys0, uint32_t len,
                               uint32_t to_dense, hipStream_t s);
+hipError_t pk_launch_bank_list(const PkBankArgs& a, hipStream_t s);
+hipError_t pk_launch_bank_copy(const PkBankArgs& a, hipStream_t s);
 
 namespace {
 
@@ -270,6 +272,18 @@ struct pk_handle {
     uint32_t* info_bits = nullptr; // [PK_INFO_BITS_WORDS][npad]
     uint32_t cap_log2 = 0;
     double reward_scale = 4.0;
+    // savestate bank (pk_bank_create; pk_layout.h PkBankArgs): the slots, then the per-range lists
+    // [2 * ngroups] counters (envs, sub-blocks), [npad] env ids, [npad] sub-block ids, and the
+    // validated slot of every env
+    uint32_t bank_n = 0;
+    uint8_t* b_mem = nullptr;
+    uint32_t* b_regs = nullptr;
+    uint32_t* b_lat = nullptr;
+    uint8_t* b_screen = nullptr;
+    uint8_t* b_filled = nullptr;
+    uint32_t* b_rejects = nullptr;
+    uint32_t* b_lists = nullptr;
+    int32_t* b_src = nullptr;
     // profiling: 4 events per profiled step (start, after K1, after K2, after K4+K3)
     bool prof = false;
     std::vector<hipEvent_t> ev_pool;
@@ -308,7 +322,8 @@ void pk_destroy(pk_handle* h) {
     for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
     void* ptrs[] = {h->mem, h->regs, h->lat, h->screen, h->rom, h->ucode, h->bank_slot, h->slot_bank, h->t_mem, h->t_regs,
                     h->t_lat, h->t_screen, h->scratch, h->rs, h->rsd, h->seen, h->mask, h->cutc, h->obs, h->reload,
-                    h->lists, h->dbg, h->info, h->info_flag, h->heat, h->info_bits, h->bank_slot_s, h->slot_bank_s};
+                    h->lists, h->dbg, h->info, h->info_flag, h->heat, h->info_bits, h->bank_slot_s, h->slot_bank_s,
+                    h->b_mem, h->b_regs, h->b_lat, h->b_screen, h->b_filled, h->b_rejects, h->b_lists, h->b_src};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     delete h;
@@ -1018,6 +1033,196 @@ int pk_launch_shape(pk_handle* h, uint32_t env0, uint32_t count, uint32_t* out5)
     out5[2] = a.block;
     out5[3] = a.prio;
     out5[4] = a.all_staged;
+    return 0;
+}
+
+// ---- savestate bank -------------------------------------------------------------------------
+
+static void bank_free(pk_handle* h) {
+    void* ptrs[] = {h->b_mem, h->b_regs, h->b_lat, h->b_screen, h->b_filled, h->b_rejects, h->b_lists, h->b_src};
+    for (void* p : ptrs)
+        if (p) (void)hipFree(p);
+    h->b_mem = h->b_screen = h->b_filled = nullptr;
+    h->b_regs = h->b_lat = h->b_rejects = h->b_lists = nullptr;
+    h->b_src = nullptr;
+    h->bank_n = 0;
+}
+
+int pk_bank_create(pk_handle* h, uint32_t n_slots) {
+    if (!h) return fail(-EINVAL, "null handle");
+    if (h->bank_n) return fail(-EEXIST, "the handle already has a bank of %u slots", h->bank_n);
+    if (n_slots == 0 || n_slots > PK_BANK_MAX_SLOTS) return fail(-EINVAL, "n_slots must be 1..%u", PK_BANK_MAX_SLOTS);
+    HIPCHK(hipSetDevice(h->device));
+    const size_t lists = (2 * (size_t)h->ngroups + 2 * (size_t)h->npad) * 4;
+    hipError_t e = hipMalloc((void**)&h->b_mem, (size_t)n_slots * PK_PHYS);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->b_regs, (size_t)n_slots * PK_BANK_REGS * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->b_lat, (size_t)n_slots * 3 * PK_ROWS * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->b_screen, (size_t)n_slots * PK_SCREEN);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->b_filled, n_slots);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->b_rejects, 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->b_lists, lists);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->b_src, (size_t)h->npad * 4);
+    if (e != hipSuccess) {
+        bank_free(h);
+        (void)hipGetLastError();
+        return fail(-ENOMEM, "bank of %u slots (%zu bytes each): %s", n_slots,
+                    (size_t)PK_PHYS + PK_BANK_REGS * 4 + 3 * PK_ROWS * 4 + PK_SCREEN, hipGetErrorString(e));
+    }
+    e = hipMemset(h->b_filled, 0, n_slots);
+    if (e == hipSuccess) e = hipMemset(h->b_rejects, 0, 4);
+    if (e == hipSuccess) e = hipMemset(h->b_lists, 0, lists);
+    if (e == hipSuccess) e = hipMemset(h->b_src, 0xFF, (size_t)h->npad * 4);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        bank_free(h);
+        return fail(-EIO, "bank setup failed: %s", hipGetErrorString(e));
+    }
+    h->bank_n = n_slots;
+    return 0;
+}
+
+uint32_t pk_bank_slots(const pk_handle* h) { return h ? h->bank_n : 0; }
+
+static int check_bank(pk_handle* h, uint32_t slot) {
+    if (!h) return fail(-EINVAL, "null handle");
+    if (!h->bank_n) return fail(-ENOENT, "the handle has no bank (pk_bank_create)");
+    if (slot >= h->bank_n) return fail(-EINVAL, "slot %u out of range (%u slots)", slot, h->bank_n);
+    return 0;
+}
+
+int pk_bank_put(pk_handle* h, uint32_t slot, const uint8_t* in, uint64_t len) {
+    int rc;
+    if ((rc = check_bank(h, slot))) return rc;
+    if (!in) return fail(-EINVAL, "null argument");
+    Template t;
+    if ((rc = parse_v9(in, len, t))) return rc;
+    uint32_t regs[PK_BANK_REGS] = {0};
+    memcpy(regs, t.regs, sizeof t.regs);
+    const uint8_t one = 1;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(h->b_mem + (size_t)slot * PK_PHYS, t.mem.data(), PK_PHYS, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->b_regs + (size_t)slot * PK_BANK_REGS, regs, sizeof regs, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->b_lat + (size_t)slot * 3 * PK_ROWS, t.lat, sizeof t.lat, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->b_screen + (size_t)slot * PK_SCREEN, t.screen.data(), PK_SCREEN, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->b_filled + slot, &one, 1, hipMemcpyHostToDevice));
+    return 0;
+}
+
+int pk_bank_get(pk_handle* h, uint32_t slot, uint8_t* out, uint64_t len) {
+    int rc;
+    if ((rc = check_bank(h, slot))) return rc;
+    if (!out) return fail(-EINVAL, "null argument");
+    if (len < S_SIZE) return fail(-EINVAL, "buffer too small for a v9 state");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipDeviceSynchronize());
+    uint8_t filled = 0;
+    HIPCHK(hipMemcpy(&filled, h->b_filled + slot, 1, hipMemcpyDeviceToHost));
+    if (!filled) return fail(-ENOENT, "slot %u is empty", slot);
+    std::vector<uint8_t> mem(PK_PHYS), screen(PK_SCREEN);
+    uint32_t regs[PK_BANK_REGS], lat[3 * PK_ROWS];
+    HIPCHK(hipMemcpy(mem.data(), h->b_mem + (size_t)slot * PK_PHYS, PK_PHYS, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(regs, h->b_regs + (size_t)slot * PK_BANK_REGS, sizeof regs, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(lat, h->b_lat + (size_t)slot * 3 * PK_ROWS, sizeof lat, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(screen.data(), h->b_screen + (size_t)slot * PK_SCREEN, PK_SCREEN, hipMemcpyDeviceToHost));
+    export_v9(h->tmpl, regs, mem.data(), lat, screen.data(), out);
+    return 0;
+}
+
+// the bank lists of an env range, laid out like the reset lists (list_cnt / list_ids): counters
+// [2 * (env0 / 64)] (envs) and [+1] (sub-blocks), ids from env0 — the bank's own, so a bank call
+// and a reset of two ranges on two streams never share one
+static PkBankArgs bank_args(pk_handle* h, uint32_t mode, const int32_t* slots, uint32_t env0, uint32_t env1) {
+    PkBankArgs a;
+    memset(&a, 0, sizeof a);
+    a.mem = h->mem; a.regs = h->regs; a.lat = h->lat; a.screen = h->screen;
+    a.b_mem = h->b_mem; a.b_regs = h->b_regs; a.b_lat = h->b_lat; a.b_screen = h->b_screen;
+    a.b_filled = h->b_filled; a.b_rejects = h->b_rejects;
+    a.slot_of_env = slots; a.src = h->b_src;
+    a.cnt = h->b_lists + 2u * (env0 / PK_LANES);
+    a.ids = h->b_lists + 2u * h->ngroups + env0;
+    a.subs = h->b_lists + 2u * h->ngroups + h->npad + env0;
+    a.tcnt = list_cnt(h, env0, 0); a.tids = list_ids(h, env0, 0);
+    a.n_slots = h->bank_n; a.mode = mode; a.n = h->n; a.npad = h->npad; a.lat_stride = (uint32_t)h->lat_stride;
+    a.env0 = env0; a.env1 = env1; a.ilv_sh = h->ilv_sh;
+    return a;
+}
+
+static int bank_move(pk_handle* h, uint32_t mode, const int32_t* slots, uint32_t env0, uint32_t count, void* stream) {
+    int rc;
+    if ((rc = check_range(h, env0, count))) return rc;
+    if (!h->bank_n) return fail(-ENOENT, "the handle has no bank (pk_bank_create)");
+    if (!slots) return fail(-EINVAL, "slot_of_env_dev is required");
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    PkBankArgs a = bank_args(h, mode, slots, env0, env0 + count);
+    HIPCHK(hipMemsetAsync(a.cnt, 0, 8, s));
+    HIPCHK(pk_launch_bank_list(a, s));
+    HIPCHK(pk_launch_bank_copy(a, s));
+    return 0;
+}
+
+int pk_bank_save(pk_handle* h, const int32_t* slots, uint32_t env0, uint32_t count, void* stream) {
+    return bank_move(h, PK_BANK_SAVE, slots, env0, count, stream);
+}
+
+int pk_bank_load(pk_handle* h, const int32_t* slots, uint32_t env0, uint32_t count, void* stream) {
+    return bank_move(h, PK_BANK_LOAD, slots, env0, count, stream);
+}
+
+// template_reset with a slot per env: the selected envs with a usable slot reload from it (bank
+// lists), the others from the handle's template — through the range's own reset list, which
+// pk_bank_list_kernel fills in pk_list_kernel's place (same range, same stream as any other reset
+// of the range)
+static int bank_reset(pk_handle* h, const uint8_t* sel, const int32_t* slots, uint32_t env0, uint32_t env1, void* stream) {
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    PkBankArgs b = bank_args(h, PK_BANK_RESET, slots, env0, env1);
+    b.sel = sel;
+    HIPCHK(hipMemsetAsync(b.cnt, 0, 8, s));
+    HIPCHK(hipMemsetAsync(b.tcnt, 0, 4, s));
+    HIPCHK(pk_launch_bank_list(b, s));
+    PkResetArgs a;
+    a.mem = h->mem; a.regs = h->regs; a.lat = h->lat; a.screen = h->screen;
+    a.tmpl_mem = h->t_mem; a.tmpl_regs = h->t_regs; a.tmpl_lat = h->t_lat; a.tmpl_screen = h->t_screen;
+    a.cnt = b.tcnt; a.ids = b.tids; a.n = h->n; a.npad = h->npad;
+    a.lat_stride = (uint32_t)h->lat_stride; a.env0 = env0; a.env1 = env1; a.ilv_sh = h->ilv_sh;
+    HIPCHK(pk_launch_reset(a, s));
+    HIPCHK(pk_launch_bank_copy(b, s));
+    return 0;
+}
+
+int pk_reset_from(pk_handle* h, uint32_t env0, uint32_t count, const uint8_t* mask, const int32_t* slots, void* stream) {
+    if (!slots) return pk_reset_range(h, env0, count, mask, stream);
+    int rc;
+    if ((rc = check_range(h, env0, count))) return rc;
+    if (!h->bank_n) return fail(-ENOENT, "the handle has no bank (pk_bank_create)");
+    const uint32_t env1 = env0 + count;
+    if (!(h->flags & PK_F_REWARD)) return bank_reset(h, mask, slots, env0, env1, stream);
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    PkRewardArgs r = reward_args(h, env0, env1);
+    r.env_mask = mask;
+    HIPCHK(pk_launch_rreset_pre(r, s));
+    if ((rc = bank_reset(h, h->reload, slots, env0, env1, stream))) return rc;
+    HIPCHK(pk_launch_rreset_post(r, s));
+    HIPCHK(hipMemsetAsync(list_cnt(h, env0, 1), 0, 4, s));
+    HIPCHK(pk_launch_list(mask, env0, env1, list_cnt(h, env0, 1), list_ids(h, env0, 1), s));
+    r.ocnt = list_cnt(h, env0, 1);
+    r.oids = list_ids(h, env0, 1);
+    HIPCHK(pk_launch_obs(r, s));
+    return 0;
+}
+
+int pk_bank_rejects(pk_handle* h, uint64_t* out) {
+    if (!h || !out) return fail(-EINVAL, "null argument");
+    if (!h->bank_n) return fail(-ENOENT, "the handle has no bank (pk_bank_create)");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipDeviceSynchronize());
+    uint32_t v = 0;
+    HIPCHK(hipMemcpy(&v, h->b_rejects, 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemset(h->b_rejects, 0, 4));
+    *out = v;
     return 0;
 }
 

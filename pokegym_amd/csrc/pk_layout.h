@@ -169,3 +169,40 @@ struct PkResetArgs {
     uint32_t env0, env1;         // env range the list was built over
     uint32_t ilv_sh;             // image interleave (pk_img_off)
 };
+
+// Savestate bank (pk_bank_* / pk_reset_from): n_slots slots of machine state in device memory, each
+// what a parsed v9 template holds — the dense PK_PHYS-byte RAM image (linear, not interleaved),
+// PK_BANK_REGS register words (PK_NREGS used), 3 x 144 latches and the 144 x 160 screen, one
+// array per part so every part of a slot starts 16-byte aligned: 74,512 bytes per slot.
+#define PK_BANK_REGS 20u
+#define PK_BANK_MAX_SLOTS 65536u
+// RAM-image tile of the bank <-> image transposition: PK_BANK_TILE bytes = (PK_BANK_TILE >> sh)
+// phys rows of one sub-block's 1 << sh envs, padded by one word per env in LDS
+#define PK_BANK_TILE 16384u
+enum { PK_BANK_LOAD = 0, PK_BANK_SAVE = 1, PK_BANK_RESET = 2 };
+
+struct PkBankArgs {
+    uint8_t* mem;                // lane-interleaved RAM images
+    uint32_t* regs;
+    uint32_t* lat;
+    uint8_t* screen;
+    uint8_t* b_mem;              // [n_slots][PK_PHYS]
+    uint32_t* b_regs;            // [n_slots][PK_BANK_REGS]
+    uint32_t* b_lat;             // [n_slots][3 * 144]
+    uint8_t* b_screen;           // [n_slots][144 * 160]
+    uint8_t* b_filled;           // [n_slots]
+    uint32_t* b_rejects;         // envs that named a slot >= n_slots or an empty slot
+    const int32_t* slot_of_env;  // caller's i32[n]
+    const uint8_t* sel;          // PK_BANK_RESET: envs that reload (u8[n]; null = all)
+    int32_t* src;                // [npad] validated slot of every env of the range, -1 = takes no part
+    uint32_t* cnt;               // the range's bank lists: [0] envs, [1] sub-blocks ...
+    uint32_t* ids;               // ... env ids (from env0) ...
+    uint32_t* subs;              // ... and the sub-blocks (env >> ilv_sh) that hold one
+    uint32_t* tcnt;              // PK_BANK_RESET: the range's template reset list (pk_list_kernel's),
+    uint32_t* tids;              // taking the reloading envs without a usable slot
+    uint32_t n_slots;
+    uint32_t mode;               // PK_BANK_*
+    uint32_t n, npad, lat_stride;
+    uint32_t env0, env1;
+    uint32_t ilv_sh;
+};

@@ -149,6 +149,69 @@ class BatchedEmulator:
         check(self._L.pk_reset(self._h, mp, self._stream()), "pk_reset")
         return self.obs if self.reward else self.screen
 
+    # -- savestate bank (stream-ordered except create / put / get / rejects) --------------
+    def bank_create(self, n_slots: int):
+        """Give the handle a bank of n_slots savestate slots in device memory (pk_bank_create; once)."""
+        check(self._L.pk_bank_create(self._h, int(n_slots)), "pk_bank_create")
+
+    @property
+    def bank_slots(self) -> int:
+        return int(self._L.pk_bank_slots(self._h))
+
+    def bank_put(self, slot: int, state: bytes):
+        """Parse a v9 savestate into a slot (pk_bank_put; synchronous)."""
+        a, p = _u8p(state)
+        check(self._L.pk_bank_put(self._h, int(slot), p, len(a)), "pk_bank_put")
+
+    def bank_get(self, slot: int) -> bytes:
+        """The v9 savestate a filled slot holds (pk_bank_get; synchronous)."""
+        out = np.zeros(STATE_V9_BYTES, np.uint8)
+        check(self._L.pk_bank_get(self._h, int(slot), out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), len(out)),
+              "pk_bank_get")
+        return out.tobytes()
+
+    def _slots_ptr(self, slot_of_env: torch.Tensor):
+        if (slot_of_env.dtype != torch.int32 or slot_of_env.device != self.device or slot_of_env.numel() != self.n
+                or not slot_of_env.is_contiguous()):
+            raise ValueError("slot_of_env must be a contiguous int32 tensor of n_envs elements on the emulator's device")
+        return ctypes.c_void_p(slot_of_env.data_ptr())
+
+    def bank_save(self, slot_of_env: torch.Tensor, env0: int = 0, count: int | None = None):
+        """slot[slot_of_env[e]] <- env e for the envs of [env0, env0 + count) with a slot >= 0
+        (pk_bank_save, on the current stream; slot_of_env is a FULL-size int32 tensor)."""
+        count = self.n - env0 if count is None else count
+        check(self._L.pk_bank_save(self._h, self._slots_ptr(slot_of_env), env0, count, self._stream()), "pk_bank_save")
+
+    def bank_load(self, slot_of_env: torch.Tensor, env0: int = 0, count: int | None = None):
+        """env e <- slot[slot_of_env[e]] with load_env's semantics (pk_bank_load, on the current stream)."""
+        count = self.n - env0 if count is None else count
+        check(self._L.pk_bank_load(self._h, self._slots_ptr(slot_of_env), env0, count, self._stream()), "pk_bank_load")
+
+    def reset_range_from(self, env0: int, count: int, slot_of_env: torch.Tensor, mask: torch.Tensor | None = None):
+        """reset_range with the template of env e taken from slot[slot_of_env[e]] (a negative slot:
+        the emulator's own template) — pk_reset_from on the current stream."""
+        mp = None
+        if mask is not None:
+            if mask.dtype != torch.uint8 or mask.device != self.device or mask.numel() != self.n or not mask.is_contiguous():
+                raise ValueError("reset_range_from mask must be a contiguous uint8 tensor of n_envs elements on the device")
+            mp = ctypes.c_void_p(mask.data_ptr())
+        check(self._L.pk_reset_from(self._h, env0, count, mp, self._slots_ptr(slot_of_env), self._stream()), "pk_reset_from")
+        obs = self.obs if self.reward else self.screen
+        return obs[env0:env0 + count]
+
+    def reset_from(self, slot_of_env: torch.Tensor, mask: torch.Tensor | None = None):
+        """reset() with a slot per env (pk_reset_from over every env).  Returns the obs."""
+        if mask is not None:
+            mask = mask.to(device=self.device, dtype=torch.uint8).contiguous()
+        self.reset_range_from(0, self.n, slot_of_env, mask)
+        return self.obs if self.reward else self.screen
+
+    def bank_rejects(self) -> int:
+        """Envs whose slot was out of range or empty since the last call (pk_bank_rejects; synchronous)."""
+        v = ctypes.c_uint64()
+        check(self._L.pk_bank_rejects(self._h, ctypes.byref(v)), "pk_bank_rejects")
+        return int(v.value)
+
     def set_episode_params(self, max_episode_steps: int, reward_scale: float):
         """Episode length and reward scale of the following steps (Environment.reset's arguments,
         environment.py:1233, :1258-1259); call before the reset they belong to."""

@@ -234,10 +234,19 @@ class VecEnv:
     def __init__(self, num_envs: int, rom_path=None, state_path=None, rom: bytes | None = None, state: bytes | None = None,
                  device: int | None = None, max_episode_steps: int = 20480, reward_scale: float = 4.0,
                  reload_on_reset: bool = False, env_offset: int = 0, log_interval: int = 128, emulator=None,
-                 heatmap: bool = False, reward: bool = True, power_on: bool = False, batch_size: int | None = None):
+                 heatmap: bool = False, reward: bool = True, power_on: bool = False, batch_size: int | None = None,
+                 state_pool=None, pool_seed: int = 0, bank_slots: int = 0):
         """reward=False: the screen-obs env of configs[3] — obs is the (144, 160) u8 screen, rewards are
         0 and episodes end at max_episode_steps.  power_on=True starts (and resets) every env from
-        the cartridge's power-on state instead of a savestate."""
+        the cartridge's power-on state instead of a savestate.
+
+        state_pool (a list of v9 savestates, bytes or paths) puts the states into a device savestate
+        bank; every reset, the auto-resets included, then starts each env from a slot drawn on the
+        device (a torch.Generator seeded with pool_seed) — the reference's get_random_state /
+        load_random_state (environment.py:51, :116, :219-227) for a whole batch.  `start_slots` is
+        the slot every env last started from.  bank_slots adds that many free slots after the
+        pool's, for save_to_bank / load_from_bank.  With neither, no bank exists and every call is
+        the one made without this feature."""
         self.batch_size = batch_size or num_envs
         if num_envs % self.batch_size:
             raise ValueError("batch_size must divide num_envs")
@@ -295,6 +304,74 @@ class VecEnv:
         self._log_wait = 0
         self._snap_events = [torch.cuda.Event() for _ in range(self.num_batches)] if self.num_batches > 1 else []
         self._snap_err = torch.zeros_like(self.sticky_errors) if self.sticky_errors is not None else None
+        # savestate bank: the pool's states in slots [0, pool_size), bank_slots free ones after them
+        self.pool_size = 0
+        self._slots = self._pool_gen = None
+        if state_pool is not None or bank_slots:
+            pool = [st if isinstance(st, (bytes, bytearray)) else _read(st) for st in (state_pool or [])]
+            if state_pool is not None and not pool:
+                raise ValueError("state_pool is empty")
+            self.emu.bank_create(len(pool) + int(bank_slots))
+            for k, st in enumerate(pool):
+                self.emu.bank_put(k, st)
+            self.pool_size = len(pool)
+            if pool:
+                self._pool_gen = torch.Generator(device=self.device)
+                self._pool_gen.manual_seed(int(pool_seed))
+                # slot each emulator env last started from; padding envs keep -1 (the template)
+                self._slots = torch.full((n_phys,), -1, dtype=torch.int32, device=self.device)
+
+    def _draw_slots(self, psl: slice, done: torch.Tensor | None = None):
+        """Draw a pool slot for the envs of emulator range psl (those with done[e] != 0) on the
+        current stream; the others keep the slot they started from."""
+        draw = torch.randint(0, self.pool_size, (psl.stop - psl.start,), generator=self._pool_gen,
+                             device=self.device, dtype=torch.int32)
+        cur = self._slots[psl]
+        if done is None:
+            cur.copy_(draw)
+        else:
+            torch.where(done != 0, draw, cur, out=cur)
+
+    @property
+    def start_slots(self) -> torch.Tensor:
+        """Pool slot every env last started an episode from (int32, env order)."""
+        if self._slots is None:
+            raise RuntimeError("VecEnv(state_pool=...) draws start slots")
+        return self._logical(self._slots).clone()
+
+    def _bank_map(self, envs, slots) -> torch.Tensor:
+        """Full-size slot_of_env (emulator order) naming slots[i] for env envs[i], -1 elsewhere."""
+        if not self.emu.bank_slots:
+            raise RuntimeError("VecEnv(state_pool=... or bank_slots=...) makes the bank")
+        envs = torch.as_tensor(envs, device=self.device).reshape(-1).long()
+        slots = torch.as_tensor(slots, device=self.device).reshape(-1).to(torch.int32)
+        if envs.numel() != slots.numel():
+            raise ValueError("envs and slots must have the same length")
+        phys = (envs // self.batch_size) * self.slot + envs % self.batch_size
+        out = torch.full((self.emu.n,), -1, dtype=torch.int32, device=self.device)
+        out[phys] = slots
+        return out
+
+    def save_to_bank(self, envs, slots, check: bool = True):
+        """Save env envs[i] into bank slot slots[i] (host lists or device tensors, env indices as
+        everywhere in this class) on the current stream, after it has joined the sub-batch streams:
+        a pipeline join — steps in flight finish first — not a host sync.  check=True rejects a
+        slot named twice (the slot would hold a mixture), which reads the slots back and so does
+        sync the host; pass check=False inside a training loop."""
+        if check:
+            s = torch.as_tensor(slots).reshape(-1)
+            if torch.unique(s).numel() != s.numel():
+                raise ValueError("save_to_bank: a slot is named twice")
+        self._join_streams()
+        self.emu.bank_save(self._bank_map(envs, slots))
+
+    def load_from_bank(self, envs, slots):
+        """Load bank slot slots[i] into env envs[i] (pk_bank_load: machine state only, the episode's
+        step counter and reward bookkeeping survive) on the current stream, after a pipeline join
+        like save_to_bank's.  An empty or out-of-range slot leaves its env alone and counts in
+        emu.bank_rejects()."""
+        self._join_streams()
+        self.emu.bank_load(self._bank_map(envs, slots))
 
     def _range(self, b: int) -> slice:
         return slice(b * self.batch_size, (b + 1) * self.batch_size)
@@ -327,7 +404,12 @@ class VecEnv:
             mes = max_episode_steps if max_episode_steps is not None else getattr(self.emu, "max_episode_steps", 20480)
             rsc = reward_scale if reward_scale is not None else getattr(self.emu, "reward_scale", 4.0)
             self.emu.set_episode_params(mes, rsc)
-        obs = self._logical(self.emu.reset())
+        if self._slots is None:
+            obs = self._logical(self.emu.reset())
+        else:
+            for b in range(self.num_batches):
+                self._draw_slots(self._prange(b))
+            obs = self._logical(self.emu.reset_from(self._slots))
         self.t = 0
         self._log_wait = 0
         if self.sticky_errors is not None:
@@ -367,7 +449,13 @@ class VecEnv:
         terminals = term.to(torch.bool)
         truncations = trunc.to(torch.bool)
         # auto-reset the finished envs (no host sync); their obs is the first obs of the next episode
-        if self.num_batches == 1:
+        if self._slots is not None:
+            self._draw_slots(psl, term)
+            if self.num_batches == 1:
+                self.emu.reset_from(self._slots, term)
+            else:
+                self.emu.reset_range_from(psl.start, self.batch_size, self._slots, self.emu.terminals)
+        elif self.num_batches == 1:
             self.emu.reset(term)
         else:
             self.emu.reset_range(psl.start, self.batch_size, self.emu.terminals)
