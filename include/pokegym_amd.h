@@ -29,6 +29,8 @@
  *   pk_bank_load     load_first/last/random_state,     environment.py:219-227, :215-217
  *                    load_pokemon_center_state
  *   pk_reset_from    reset from a state of the pool    environment.py:116, :122, :1241-1242
+ *   pk_bank_checkpoint / pk_bank_resume   no reference equivalent: a whole episode (machine state
+ *                    and the Environment's per-episode attributes) saved to and continued from a slot
  * With PK_F_REWARD, pk_step also runs the reward stack of Environment.step
  * (environment.py:1338-1612) and pk_reset follows Environment.reset (:1233-1334).
  */
@@ -41,7 +43,7 @@
 extern "C" {
 #endif
 
-#define PK_ABI_VERSION 7
+#define PK_ABI_VERSION 8
 #define PK_STATE_V9_BYTES 142610u
 #define PK_SCREEN_ROWS 144u
 #define PK_SCREEN_COLS 160u
@@ -186,7 +188,8 @@ int pk_snapshot_range(pk_handle* h, uint32_t env0, uint32_t count, uint8_t* host
  * 3 x 144 scanline latches and the 144 x 160 screen, about 74.5 KB.  The step counter and the
  * per-step bookkeeping registers are not machine state; a slot stores them as a freshly parsed
  * state has them (0).  The reward stack's bookkeeping (seen-coordinate sets, heat maps, the
- * per-episode attributes) is NOT in a slot: a load leaves it as it is, a reset rebuilds it.
+ * per-episode attributes) is NOT in this machine part of a slot: a load leaves it as it is, a reset
+ * rebuilds it.  A bank with episode parts (below) can carry it next to the machine part.
  *
  * pk_bank_create (synchronous): once per handle, before any other bank call; n_slots in
  * 1..65536.  On failure (second call, bad n_slots, out of memory) the handle stays usable and
@@ -223,8 +226,40 @@ int pk_bank_load(pk_handle* h, const int32_t* slot_of_env_dev, uint32_t env0, ui
  * slot_of_env_dev == NULL is exactly pk_reset_range. */
 int pk_reset_from(pk_handle* h, uint32_t env0, uint32_t count, const uint8_t* env_mask_dev,
                   const int32_t* slot_of_env_dev, void* stream);
-/* Envs rejected by pk_bank_save / pk_bank_load / pk_reset_from since the last call; clears the
- * counter (synchronous). */
+/* Episode checkpoints.  After pk_bank_enable_episodes every slot can carry, next to its machine
+ * part, the rest of an episode: the env's step counter and the lane registers the machine part
+ * normalises, every per-episode attribute of the reward stack (the flags that survive resets and
+ * the error code included: a frozen env checkpoints as frozen), the seen-coordinate set, the
+ * visited mask of the current map and the cut coordinates.  An env resumed from such a slot and
+ * fed the same actions produces the rewards, dones, observations, info records and machine
+ * state of the env it was saved from, bit for bit.  Three things belong to the env and not to
+ * the episode and are never restored: the tag of the env's seen table, its reset count (which
+ * decides the env's template reloads) and the PK_F_HEATMAP counts_map with its running sum (the
+ * "coord" info field) — the map stays with the env and keeps counting what is played on it.
+ *
+ * Memory: an episode part is 4 * cap + 8,448 bytes plus a 272-byte record, cap = the seen set's
+ * capacity, the power of two >= max((max_episode_steps + 2) * 4 / 3, 1024): 139,792 bytes per
+ * slot at the default 20,480 steps, besides the 74,512 of the machine part; size n_slots by that.
+ *
+ * pk_bank_enable_episodes (synchronous): once per handle, needs a bank and PK_F_REWARD; on
+ * failure the handle is unchanged.  pk_bank_has_episodes: 1 after it, else 0.  Without it
+ * pk_bank_checkpoint / pk_bank_resume fail with a negative code and change nothing.
+ *   pk_bank_checkpoint  pk_bank_save, plus the episode part; both parts are marked filled.
+ *   pk_bank_resume      pk_bank_load, plus the episode part and the step counter, then the
+ *                       observation of the resumed envs is rebuilt (pk_obs_ptr shows the resumed
+ *                       state before the next step).  Many envs may resume from one slot.
+ * Arguments, ordering and concurrency are pk_bank_save's and pk_bank_load's.  A slot >= n_slots,
+ * an empty slot or (resume) a slot without an episode part — one filled by pk_bank_put or
+ * pk_bank_save, which leave the episode part empty — is a reject: the env is untouched in every
+ * part and counted.  When pk_set_episode_params grows the seen set, the episode parts of all
+ * slots are emptied (their tables are reallocated at the new size): a later resume from an older
+ * checkpoint is a reject; the machine parts are kept. */
+int pk_bank_enable_episodes(pk_handle* h);
+int pk_bank_has_episodes(const pk_handle* h);
+int pk_bank_checkpoint(pk_handle* h, const int32_t* slot_of_env_dev, uint32_t env0, uint32_t count, void* stream);
+int pk_bank_resume(pk_handle* h, const int32_t* slot_of_env_dev, uint32_t env0, uint32_t count, void* stream);
+/* Envs rejected by pk_bank_save / pk_bank_load / pk_reset_from / pk_bank_checkpoint /
+ * pk_bank_resume since the last call; clears the counter (synchronous). */
 int pk_bank_rejects(pk_handle* h, uint64_t* out);
 
 /* Emulated instructions executed by the last pk_step, summed over envs (synchronous). */

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # PK_LIB selects an alternative in-tree build (A/B kernel experiments); default: lib/libpokegym_amd.so
 LIB_PATH = os.environ.get("PK_LIB") or os.path.join(HERE, "lib", "libpokegym_amd.so")
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 PK_F_RENDER = 1
 PK_F_REWARD = 2
 PK_F_RELOAD_ON_RESET = 4
@@ -33,7 +33,8 @@ EXPORTS = ("pk_create", "pk_destroy", "pk_last_error", "pk_abi_version", "pk_res
            "pk_snapshot_range", "pk_render_latched", "pk_step_range", "pk_reset_range",
            "pk_set_episode_params", "pk_launch_shape",
            "pk_bank_create", "pk_bank_slots", "pk_bank_put", "pk_bank_get", "pk_bank_save", "pk_bank_load",
-           "pk_reset_from", "pk_bank_rejects")
+           "pk_reset_from", "pk_bank_rejects",
+           "pk_bank_enable_episodes", "pk_bank_has_episodes", "pk_bank_checkpoint", "pk_bank_resume")
 
 
 class PkConfig(ctypes.Structure):
@@ -101,6 +102,7 @@ def bind(L):
     L.pk_profile_read.argtypes = [vp, dp, dp, dp, ctypes.POINTER(ctypes.c_uint64)]
     bind_v2(L)
     bind_v7(L)
+    bind_v8(L)
 
 
 def bind_v2(L):
@@ -142,6 +144,16 @@ def bind_v7(L):
     L.pk_bank_load.argtypes = [vp, vp, u32, u32, vp]
     L.pk_reset_from.argtypes = [vp, u32, u32, vp, vp, vp]
     L.pk_bank_rejects.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
+
+
+def bind_v8(L):
+    """argtypes of the episode checkpoints (ABI v8; shared with the host-simulation test build)."""
+    vp = ctypes.c_void_p
+    u32 = ctypes.c_uint32
+    L.pk_bank_enable_episodes.argtypes = [vp]
+    L.pk_bank_has_episodes.argtypes = [vp]
+    L.pk_bank_checkpoint.argtypes = [vp, vp, u32, u32, vp]
+    L.pk_bank_resume.argtypes = [vp, vp, u32, u32, vp]
 
 
 def check(rc: int, what: str):

@@ -41,6 +41,7 @@ hipError_t pk_launch_ram_copy(uint8_t* mem, uint8_t* dense, uint32_t n, uint32_t
                               uint32_t to_dense, hipStream_t s);
 hipError_t pk_launch_bank_list(const PkBankArgs& a, hipStream_t s);
 hipError_t pk_launch_bank_copy(const PkBankArgs& a, hipStream_t s);
+hipError_t pk_launch_ep_move(const PkEpArgs& a, hipStream_t s);
 
 namespace {
 
@@ -284,6 +285,12 @@ struct pk_handle {
     uint32_t* b_rejects = nullptr;
     uint32_t* b_lists = nullptr;
     int32_t* b_src = nullptr;
+    // episode parts of the slots (pk_bank_enable_episodes; pk_reward.h PkEpArgs), null without them
+    uint32_t* e_fields = nullptr;
+    uint32_t* e_seen = nullptr;
+    uint32_t* e_mask = nullptr;
+    uint32_t* e_cutc = nullptr;
+    uint8_t* b_ep_filled = nullptr;
     // profiling: 4 events per profiled step (start, after K1, after K2, after K4+K3)
     bool prof = false;
     std::vector<hipEvent_t> ev_pool;
@@ -323,7 +330,8 @@ void pk_destroy(pk_handle* h) {
     void* ptrs[] = {h->mem, h->regs, h->lat, h->screen, h->rom, h->ucode, h->bank_slot, h->slot_bank, h->t_mem, h->t_regs,
                     h->t_lat, h->t_screen, h->scratch, h->rs, h->rsd, h->seen, h->mask, h->cutc, h->obs, h->reload,
                     h->lists, h->dbg, h->info, h->info_flag, h->heat, h->info_bits, h->bank_slot_s, h->slot_bank_s,
-                    h->b_mem, h->b_regs, h->b_lat, h->b_screen, h->b_filled, h->b_rejects, h->b_lists, h->b_src};
+                    h->b_mem, h->b_regs, h->b_lat, h->b_screen, h->b_filled, h->b_rejects, h->b_lists, h->b_src,
+                    h->e_fields, h->e_seen, h->e_mask, h->e_cutc, h->b_ep_filled};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     delete h;
@@ -989,6 +997,25 @@ int pk_set_episode_params(pk_handle* h, uint32_t max_episode_steps, double rewar
             hipError_t e = pk_launch_seen_rehash(h->seen, h->cap_log2, seen, need, h->rs, h->n, h->npad, nullptr);
             if (e == hipSuccess) e = hipDeviceSynchronize();
             if (e != hipSuccess) { (void)hipFree(seen); return fail(-EIO, "seen-set rehash: %s", hipGetErrorString(e)); }
+            if (h->b_ep_filled) {
+                // the slots' seen tables follow the envs' size: reallocated, and every episode part
+                // marked empty (a resume from an older checkpoint is then a reject)
+                uint32_t* eseen = nullptr;
+                const size_t eb = (size_t)h->bank_n * (1ull << need) * 4;
+                e = hipMalloc((void**)&eseen, eb);
+                if (e == hipSuccess) e = hipMemset(eseen, 0, eb);
+                if (e == hipSuccess) e = hipMemset(h->b_ep_filled, 0, h->bank_n);
+                if (e == hipSuccess) e = hipDeviceSynchronize();
+                if (e != hipSuccess) {
+                    if (eseen) (void)hipFree(eseen);
+                    (void)hipFree(seen);
+                    (void)hipGetLastError();
+                    return fail(-ENOMEM, "episode parts of %u slots at the larger seen set (%zu bytes): %s", h->bank_n, eb,
+                                hipGetErrorString(e));
+                }
+                (void)hipFree(h->e_seen);
+                h->e_seen = eseen;
+            }
             (void)hipFree(h->seen);
             h->seen = seen;
             h->cap_log2 = need;
@@ -1039,9 +1066,12 @@ int pk_launch_shape(pk_handle* h, uint32_t env0, uint32_t count, uint32_t* out5)
 // ---- savestate bank -------------------------------------------------------------------------
 
 static void bank_free(pk_handle* h) {
-    void* ptrs[] = {h->b_mem, h->b_regs, h->b_lat, h->b_screen, h->b_filled, h->b_rejects, h->b_lists, h->b_src};
+    void* ptrs[] = {h->b_mem, h->b_regs, h->b_lat, h->b_screen, h->b_filled, h->b_rejects, h->b_lists, h->b_src,
+                    h->e_fields, h->e_seen, h->e_mask, h->e_cutc, h->b_ep_filled};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
+    h->e_fields = h->e_seen = h->e_mask = h->e_cutc = nullptr;
+    h->b_ep_filled = nullptr;
     h->b_mem = h->b_screen = h->b_filled = nullptr;
     h->b_regs = h->b_lat = h->b_rejects = h->b_lists = nullptr;
     h->b_src = nullptr;
@@ -1106,6 +1136,7 @@ int pk_bank_put(pk_handle* h, uint32_t slot, const uint8_t* in, uint64_t len) {
     HIPCHK(hipMemcpy(h->b_lat + (size_t)slot * 3 * PK_ROWS, t.lat, sizeof t.lat, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->b_screen + (size_t)slot * PK_SCREEN, t.screen.data(), PK_SCREEN, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->b_filled + slot, &one, 1, hipMemcpyHostToDevice));
+    if (h->b_ep_filled) HIPCHK(hipMemset(h->b_ep_filled + slot, 0, 1));   // machine state only: no episode part
     return 0;
 }
 
@@ -1137,7 +1168,7 @@ static PkBankArgs bank_args(pk_handle* h, uint32_t mode, const int32_t* slots, u
     memset(&a, 0, sizeof a);
     a.mem = h->mem; a.regs = h->regs; a.lat = h->lat; a.screen = h->screen;
     a.b_mem = h->b_mem; a.b_regs = h->b_regs; a.b_lat = h->b_lat; a.b_screen = h->b_screen;
-    a.b_filled = h->b_filled; a.b_rejects = h->b_rejects;
+    a.b_filled = h->b_filled; a.b_rejects = h->b_rejects; a.b_ep_filled = h->b_ep_filled;
     a.slot_of_env = slots; a.src = h->b_src;
     a.cnt = h->b_lists + 2u * (env0 / PK_LANES);
     a.ids = h->b_lists + 2u * h->ngroups + env0;
@@ -1212,6 +1243,83 @@ int pk_reset_from(pk_handle* h, uint32_t env0, uint32_t count, const uint8_t* ma
     r.oids = list_ids(h, env0, 1);
     HIPCHK(pk_launch_obs(r, s));
     return 0;
+}
+
+// ---- episode checkpoints in the bank ----------------------------------------------------------
+
+int pk_bank_has_episodes(const pk_handle* h) { return (h && h->b_ep_filled) ? 1 : 0; }
+
+int pk_bank_enable_episodes(pk_handle* h) {
+    if (!h) return fail(-EINVAL, "null handle");
+    if (!h->bank_n) return fail(-ENOENT, "the handle has no bank (pk_bank_create)");
+    if (!(h->flags & PK_F_REWARD)) return fail(-ENOTSUP, "episode checkpoints need the reward stack (PK_F_REWARD)");
+    if (h->b_ep_filled) return fail(-EEXIST, "the bank already carries episode parts");
+    static_assert(PK_NREGS <= PK_EP_RSD - PK_EP_REGS, "episode record layout");
+    HIPCHK(hipSetDevice(h->device));
+    const size_t K = h->bank_n, seen = K * (1ull << h->cap_log2) * 4;
+    uint32_t *f = nullptr, *sn = nullptr, *mk = nullptr, *cc = nullptr;
+    uint8_t* fl = nullptr;
+    hipError_t e = hipMalloc((void**)&f, K * PK_EP_WORDS * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&sn, seen);
+    if (e == hipSuccess) e = hipMalloc((void**)&mk, K * PK_MASK_WORDS * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&cc, K * PK_CUTC_CAP * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&fl, K);
+    if (e == hipSuccess) e = hipMemset(f, 0, K * PK_EP_WORDS * 4);
+    if (e == hipSuccess) e = hipMemset(sn, 0, seen);
+    if (e == hipSuccess) e = hipMemset(mk, 0, K * PK_MASK_WORDS * 4);
+    if (e == hipSuccess) e = hipMemset(cc, 0, K * PK_CUTC_CAP * 4);
+    if (e == hipSuccess) e = hipMemset(fl, 0, K);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        void* ptrs[] = {f, sn, mk, cc, fl};
+        for (void* p : ptrs)
+            if (p) (void)hipFree(p);
+        (void)hipGetLastError();
+        return fail(-ENOMEM, "episode parts of %zu slots (%zu bytes each): %s", K,
+                    (size_t)(seen / K) + (PK_MASK_WORDS + PK_CUTC_CAP + PK_EP_WORDS) * 4 + 1, hipGetErrorString(e));
+    }
+    h->e_fields = f; h->e_seen = sn; h->e_mask = mk; h->e_cutc = cc; h->b_ep_filled = fl;
+    return 0;
+}
+
+// pk_bank_save / pk_bank_load with ep set (the same lists, validation and launches), then the
+// episode mover over the same list, and for a resume the observation of the listed envs
+static int episode_move(pk_handle* h, uint32_t mode, const int32_t* slots, uint32_t env0, uint32_t count, void* stream) {
+    int rc;
+    if ((rc = check_range(h, env0, count))) return rc;
+    if (!h->bank_n) return fail(-ENOENT, "the handle has no bank (pk_bank_create)");
+    if (!h->b_ep_filled) return fail(-ENOENT, "the bank carries no episode parts (pk_bank_enable_episodes)");
+    if (!slots) return fail(-EINVAL, "slot_of_env_dev is required");
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    PkBankArgs a = bank_args(h, mode, slots, env0, env0 + count);
+    a.ep = 1;
+    HIPCHK(hipMemsetAsync(a.cnt, 0, 8, s));
+    HIPCHK(pk_launch_bank_list(a, s));
+    HIPCHK(pk_launch_bank_copy(a, s));
+    PkEpArgs p;
+    memset(&p, 0, sizeof p);
+    p.regs = h->regs; p.rs = h->rs; p.rsd = h->rsd; p.seen = h->seen; p.mask = h->mask; p.cutc = h->cutc;
+    p.e_fields = h->e_fields; p.e_seen = h->e_seen; p.e_mask = h->e_mask; p.e_cutc = h->e_cutc;
+    p.cnt = a.cnt; p.ids = a.ids; p.src = a.src;
+    p.npad = h->npad; p.nregs = PK_NREGS; p.cap_log2 = h->cap_log2; p.save = mode == PK_BANK_SAVE ? 1u : 0u;
+    p.items = count;
+    HIPCHK(pk_launch_ep_move(p, s));
+    if (mode == PK_BANK_LOAD) {
+        PkRewardArgs r = reward_args(h, env0, env0 + count);
+        r.ocnt = a.cnt;
+        r.oids = a.ids;
+        HIPCHK(pk_launch_obs(r, s));
+    }
+    return 0;
+}
+
+int pk_bank_checkpoint(pk_handle* h, const int32_t* slots, uint32_t env0, uint32_t count, void* stream) {
+    return episode_move(h, PK_BANK_SAVE, slots, env0, count, stream);
+}
+
+int pk_bank_resume(pk_handle* h, const int32_t* slots, uint32_t env0, uint32_t count, void* stream) {
+    return episode_move(h, PK_BANK_LOAD, slots, env0, count, stream);
 }
 
 int pk_bank_rejects(pk_handle* h, uint64_t* out) {

@@ -187,7 +187,8 @@ hipError_t pk_launch_done(const u32* time_reg, u32 n, u32 max_steps, u8* term, u
 // touched and a call that touches none is a few near-empty launches.
 
 // thread = env of the range: validate its slot before anything is written (a slot >= n_slots, or
-// an empty one where the slot is the source, is counted and takes no part), record it in src[],
+// an empty one where the slot is the source — for a resume, A.ep, one without an episode part
+// too — is counted and takes no part), record it in src[],
 // and list the env — on the bank list, or (PK_BANK_RESET) on the range's template reset list when
 // it reloads without a usable slot
 __global__ void __launch_bounds__(256) pk_bank_list_kernel(PkBankArgs A) {
@@ -200,7 +201,8 @@ __global__ void __launch_bounds__(256) pk_bank_list_kernel(PkBankArgs A) {
         if (s < 0) {
             s = -1;
             tmpl = A.mode == PK_BANK_RESET;
-        } else if ((u32)s >= A.n_slots || (A.mode != PK_BANK_SAVE && !A.b_filled[s])) {
+        } else if ((u32)s >= A.n_slots || (A.mode != PK_BANK_SAVE && !A.b_filled[s]) ||
+                   (A.mode == PK_BANK_LOAD && A.ep && !A.b_ep_filled[s])) {
             atomicAdd(A.b_rejects, 1u);
             s = -1;
             tmpl = A.mode == PK_BANK_RESET;
@@ -334,7 +336,10 @@ __global__ void __launch_bounds__(256) pk_bank_state_kernel(PkBankArgs A) {
                 bl[i] = v;
             }
             for (u32 q = sub; q < PK_SCREEN / 16u; q += 16u) bs[q] = es[q];
-            if (sub == 0u) A.b_filled[s] = 1;
+            if (sub == 0u) {
+                A.b_filled[s] = 1;
+                if (A.b_ep_filled) A.b_ep_filled[s] = A.ep ? 1 : 0;
+            }
         } else {
             const u32 nr = A.mode == PK_BANK_RESET ? (u32)PK_NREGS : (u32)PK_R_MISC + 1u;
             for (u32 f = sub; f < nr; f += 16u) A.regs[f * A.npad + env] = br[f];

@@ -191,6 +191,8 @@ struct PkBankArgs {
     uint32_t* b_lat;             // [n_slots][3 * 144]
     uint8_t* b_screen;           // [n_slots][144 * 160]
     uint8_t* b_filled;           // [n_slots]
+    uint8_t* b_ep_filled;        // [n_slots] the slot also holds an episode part (pk_reward.h PkEpArgs);
+                                 // null while the bank carries no episodes
     uint32_t* b_rejects;         // envs that named a slot >= n_slots or an empty slot
     const int32_t* slot_of_env;  // caller's i32[n]
     const uint8_t* sel;          // PK_BANK_RESET: envs that reload (u8[n]; null = all)
@@ -202,6 +204,8 @@ struct PkBankArgs {
     uint32_t* tids;              // taking the reloading envs without a usable slot
     uint32_t n_slots;
     uint32_t mode;               // PK_BANK_*
+    uint32_t ep;                 // pk_bank_checkpoint / pk_bank_resume: PK_BANK_SAVE marks the episode part
+                                 // filled too (a plain save marks it empty), PK_BANK_LOAD also needs it filled
     uint32_t n, npad, lat_stride;
     uint32_t env0, env1;
     uint32_t ilv_sh;

@@ -81,6 +81,44 @@ static_assert(PK_INFO_NFIELDS == PK_INFO_NSTATS + PK_INFO_NREWARD, "info record 
 #define PK_OBS_W 80u
 #define PK_OBS_BYTES (PK_OBS_H * PK_OBS_W * 4u)
 
+// Episode part of a savestate-bank slot (pk_bank_checkpoint / pk_bank_resume): what pk_bank_save
+// leaves behind of an episode, so that a resumed env continues exactly as the saved one would have.
+//   fields  u32[PK_EP_WORDS] per slot, AoS: the rs[] fields at PK_EP_RS, the raw lane registers at
+//           PK_EP_REGS (all PK_NREGS: the machine part stores PK_R_TIME / PK_R_ICOUNT /
+//           PK_R_RFLAGS as 0, PK_R_MISC as "nothing held" and drops register bits a v9 state has
+//           no room for), the rsd[] fields (f64) at PK_EP_RSD.  RS_GEN, RS_RESET_COUNT and
+//           RSD_COORD belong to the env, not to the episode: they are stored but never restored.
+//   seen    u32[cap] per slot, normalised: a live entry carries tag 1, every other word is 0
+//   mask    u32[PK_MASK_WORDS], cutc u32[PK_CUTC_CAP] per slot, as the env has them
+// Every part of a slot starts 16-byte aligned.  The PK_F_HEATMAP counts_map stays with the env.
+#define PK_EP_RS 0u
+#define PK_EP_REGS 40u
+#define PK_EP_RSD 60u
+#define PK_EP_WORDS 68u
+#define PK_EP_CHUNK 1024u     // 16-byte pieces of [seen | mask] one workgroup pass moves
+static_assert(RS_NFIELDS <= PK_EP_REGS - PK_EP_RS && 2u * RSD_NFIELDS <= PK_EP_WORDS - PK_EP_RSD &&
+              PK_EP_WORDS % 4u == 0u && PK_EP_RSD % 2u == 0u, "episode record layout");
+
+struct PkEpArgs {
+    uint32_t* regs;           // K1 lane registers [PK_NREGS][npad]
+    uint32_t* rs;             // [RS_NFIELDS][npad]
+    double* rsd;              // [RSD_NFIELDS][npad]
+    uint32_t* seen;           // [npad][cap]
+    uint32_t* mask;           // [npad][PK_MASK_WORDS]
+    uint32_t* cutc;           // [npad][PK_CUTC_CAP]
+    uint32_t* e_fields;       // [n_slots][PK_EP_WORDS]
+    uint32_t* e_seen;         // [n_slots][cap]
+    uint32_t* e_mask;         // [n_slots][PK_MASK_WORDS]
+    uint32_t* e_cutc;         // [n_slots][PK_CUTC_CAP]
+    const uint32_t* cnt;      // the range's bank list (pk_bank_list_kernel): count ...
+    const uint32_t* ids;      // ... env ids ...
+    const int32_t* src;       // ... and the validated slot of every env
+    uint32_t npad, nregs;     // nregs = PK_NREGS (<= PK_EP_RSD - PK_EP_REGS)
+    uint32_t cap_log2;
+    uint32_t save;            // 1 = checkpoint (env -> slot), 0 = resume (slot -> env)
+    uint32_t items;           // upper bound of listed envs (the range's size): sizes the grid
+};
+
 struct PkRewardArgs {
     uint8_t* mem;             // lane-interleaved RAM images (pk_layout.h)
     uint32_t* regs;           // K1 lane registers (TIME, special IO regs)

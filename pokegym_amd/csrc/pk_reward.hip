@@ -753,6 +753,90 @@ __global__ void pk_seen_rehash_kernel(const u32* old_tab, u32 old_lg, u32* new_t
 }
 
 // ---------------------------------------------------------------------------------------------
+// Episode mover (pk_bank_checkpoint / pk_bank_resume): the episode part (pk_reward.h PkEpArgs) of
+// the envs on the range's bank list <-> their validated slots.  The seen table and the visited
+// mask are linear on both sides, so a workgroup takes one listed env and PK_EP_CHUNK 16-byte
+// pieces of its [seen | mask], consecutive lanes moving consecutive pieces; untouched envs are
+// never scanned.  The seen tags are rewritten in registers on the way: a slot holds the table
+// normalised (a live entry — tag == the env's RS_GEN — with tag 1, every other word 0), a resume
+// writes the WHOLE table of the destination, live entries under the destination's own tag and 0
+// elsewhere, so no stale word of the destination can come back to life.  Hash positions do not
+// depend on the tag (seen_insert), so no entry moves.  The workgroup of an env's first chunk also
+// moves cutc (16 lanes) and the strided fields (one lane per word).  RS_GEN, RS_RESET_COUNT and
+// RSD_COORD stay the destination's; a destination that was never reset (tag 0) takes tag 1.
+__device__ __forceinline__ u32 ep_tag_out(u32 v, u32 gen) { return (gen != 0u && (v >> 24) == gen) ? (v & 0xFFFFFFu) | (1u << 24) : 0u; }
+__device__ __forceinline__ u32 ep_tag_in(u32 v, u32 gen) { return v ? (v & 0xFFFFFFu) | (gen << 24) : 0u; }
+
+__global__ void __launch_bounds__(256) pk_ep_move_kernel(PkEpArgs A) {
+    const u32 np = A.npad, cap = 1u << A.cap_log2, cap4 = cap / 4u;
+    const u32 pieces = cap4 + PK_MASK_WORDS / 4u;
+    const u32 chunks = (pieces + PK_EP_CHUNK - 1u) / PK_EP_CHUNK;
+    const u32 total = *A.cnt * chunks;
+    for (u32 w = blockIdx.x; w < total; w += gridDim.x) {
+        const u32 env = A.ids[w / chunks], c = w % chunks, s = (u32)A.src[env];
+        u32 gen = A.rs[RS_GEN * np + env];
+        if (!A.save && gen == 0u) gen = 1u;
+        uint4* es = reinterpret_cast<uint4*>(A.seen + (size_t)env * cap);
+        uint4* bs = reinterpret_cast<uint4*>(A.e_seen + (size_t)s * cap);
+        uint4* em = reinterpret_cast<uint4*>(A.mask + (size_t)env * PK_MASK_WORDS);
+        uint4* bm = reinterpret_cast<uint4*>(A.e_mask + (size_t)s * PK_MASK_WORDS);
+        const u32 q1 = (c + 1u) * PK_EP_CHUNK < pieces ? (c + 1u) * PK_EP_CHUNK : pieces;
+        for (u32 q = c * PK_EP_CHUNK + threadIdx.x; q < q1; q += blockDim.x) {
+            if (q < cap4) {
+                if (A.save) {
+                    uint4 v = es[q];
+                    v.x = ep_tag_out(v.x, gen); v.y = ep_tag_out(v.y, gen); v.z = ep_tag_out(v.z, gen); v.w = ep_tag_out(v.w, gen);
+                    bs[q] = v;
+                } else {
+                    uint4 v = bs[q];
+                    v.x = ep_tag_in(v.x, gen); v.y = ep_tag_in(v.y, gen); v.z = ep_tag_in(v.z, gen); v.w = ep_tag_in(v.w, gen);
+                    es[q] = v;
+                }
+            } else if (A.save) {
+                bm[q - cap4] = em[q - cap4];
+            } else {
+                em[q - cap4] = bm[q - cap4];
+            }
+        }
+        if (c != 0u) continue;
+        const u32 t = threadIdx.x;
+        if (t < PK_CUTC_CAP / 4u) {
+            uint4* ec = reinterpret_cast<uint4*>(A.cutc + (size_t)env * PK_CUTC_CAP);
+            uint4* bc = reinterpret_cast<uint4*>(A.e_cutc + (size_t)s * PK_CUTC_CAP);
+            if (A.save) bc[t] = ec[t];
+            else ec[t] = bc[t];
+        } else if (t >= 64u && t < 64u + PK_EP_WORDS) {
+            // one lane per word of the slot's record; the f64 fields move as their two halves
+            const u32 f = t - 64u;
+            u32* rec = A.e_fields + (size_t)s * PK_EP_WORDS;
+            u32* p = nullptr;
+            bool stays = false;   // the env's own, never restored
+            if (f < RS_NFIELDS) {
+                p = A.rs + (size_t)f * np + env;
+                stays = f == RS_GEN || f == RS_RESET_COUNT;
+            } else if (f >= PK_EP_REGS && f < PK_EP_REGS + A.nregs) {
+                p = A.regs + (size_t)(f - PK_EP_REGS) * np + env;
+            } else if (f >= PK_EP_RSD && f < PK_EP_RSD + 2u * RSD_NFIELDS) {
+                const u32 d = (f - PK_EP_RSD) >> 1;
+                p = reinterpret_cast<u32*>(A.rsd + (size_t)d * np + env) + ((f - PK_EP_RSD) & 1u);
+                stays = d == RSD_COORD;
+            }
+            if (A.save) rec[f] = p ? *p : 0u;
+            else if (p && !stays) *p = rec[f];
+            else if (f == RS_GEN && *p == 0u) *p = 1u;
+        }
+    }
+}
+
+hipError_t pk_launch_ep_move(const PkEpArgs& a, hipStream_t s) {
+    const u32 pieces = (1u << a.cap_log2) / 4u + PK_MASK_WORDS / 4u;
+    const uint64_t items = (uint64_t)a.items * ((pieces + PK_EP_CHUNK - 1u) / PK_EP_CHUNK);
+    const u32 grid = items < 65536u ? (u32)(items ? items : 1u) : 65536u;
+    hipLaunchKernelGGL(pk_ep_move_kernel, dim3(grid), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
 hipError_t pk_launch_seen_rehash(const u32* old_tab, u32 old_lg, u32* new_tab, u32 new_lg, const u32* rs, u32 n, u32 np,
                                  hipStream_t s) {
     hipLaunchKernelGGL(pk_seen_rehash_kernel, dim3((n + 255) / 256), dim3(256), 0, s, old_tab, old_lg, new_tab, new_lg, rs, n, np);

@@ -187,6 +187,30 @@ class BatchedEmulator:
         count = self.n - env0 if count is None else count
         check(self._L.pk_bank_load(self._h, self._slots_ptr(slot_of_env), env0, count, self._stream()), "pk_bank_load")
 
+    def bank_enable_episodes(self):
+        """Let the bank's slots carry episode parts (pk_bank_enable_episodes; once, synchronous; needs
+        reward=True and a bank)."""
+        check(self._L.pk_bank_enable_episodes(self._h), "pk_bank_enable_episodes")
+
+    @property
+    def bank_has_episodes(self) -> bool:
+        return bool(self._L.pk_bank_has_episodes(self._h))
+
+    def bank_checkpoint(self, slot_of_env: torch.Tensor, env0: int = 0, count: int | None = None):
+        """bank_save plus the episode part of every saved env: step counter, reward bookkeeping, seen
+        set, visited mask (pk_bank_checkpoint, on the current stream)."""
+        count = self.n - env0 if count is None else count
+        check(self._L.pk_bank_checkpoint(self._h, self._slots_ptr(slot_of_env), env0, count, self._stream()),
+              "pk_bank_checkpoint")
+
+    def bank_resume(self, slot_of_env: torch.Tensor, env0: int = 0, count: int | None = None):
+        """env e continues the episode checkpointed in slot[slot_of_env[e]]: machine state, episode
+        part and a rebuilt `obs` row (pk_bank_resume, on the current stream).  A slot without an
+        episode part leaves its env alone and counts in bank_rejects()."""
+        count = self.n - env0 if count is None else count
+        check(self._L.pk_bank_resume(self._h, self._slots_ptr(slot_of_env), env0, count, self._stream()),
+              "pk_bank_resume")
+
     def reset_range_from(self, env0: int, count: int, slot_of_env: torch.Tensor, mask: torch.Tensor | None = None):
         """reset_range with the template of env e taken from slot[slot_of_env[e]] (a negative slot:
         the emulator's own template) — pk_reset_from on the current stream."""

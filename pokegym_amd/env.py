@@ -51,6 +51,15 @@ def _read(path_or_bytes):
         return f.read()
 
 
+def _seen_cap_log2(max_episode_steps: int) -> int:
+    """log2 of the seen-coordinate set's capacity for an episode length (pk_create /
+    pk_set_episode_params: one entry per step at most, load factor <= 3/4, at least 1024)."""
+    lg = 10
+    while (1 << lg) * 3 < (int(max_episode_steps) + 2) * 4:
+        lg += 1
+    return lg
+
+
 class Base:
     """pokegym.environment.Base (environment.py:89-434): the emulator surface without the reward
     stack — step(action) runs the action and returns (render(), 0, False, False, {}) (:404-406),
@@ -235,7 +244,8 @@ class VecEnv:
                  device: int | None = None, max_episode_steps: int = 20480, reward_scale: float = 4.0,
                  reload_on_reset: bool = False, env_offset: int = 0, log_interval: int = 128, emulator=None,
                  heatmap: bool = False, reward: bool = True, power_on: bool = False, batch_size: int | None = None,
-                 state_pool=None, pool_seed: int = 0, bank_slots: int = 0):
+                 state_pool=None, pool_seed: int = 0, bank_slots: int = 0, bank_episodes: bool = False,
+                 fork_slots: int = 0):
         """reward=False: the screen-obs env of configs[3] — obs is the (144, 160) u8 screen, rewards are
         0 and episodes end at max_episode_steps.  power_on=True starts (and resets) every env from
         the cartridge's power-on state instead of a savestate.
@@ -246,7 +256,14 @@ class VecEnv:
         load_random_state (environment.py:51, :116, :219-227) for a whole batch.  `start_slots` is
         the slot every env last started from.  bank_slots adds that many free slots after the
         pool's, for save_to_bank / load_from_bank.  With neither, no bank exists and every call is
-        the one made without this feature."""
+        the one made without this feature.
+
+        bank_episodes=True (needs reward=True) lets the slots carry whole episodes: checkpoint_to_bank
+        / resume_from_bank move the machine state together with the episode's step counter and
+        reward bookkeeping, so a resumed env continues exactly as the saved one would have, and
+        this class's per-env episode return / length and start slot travel with it.  fork_slots
+        reserves that many scratch slots after the pool's and the user's for fork(): the number of
+        distinct source envs one fork() call can copy."""
         self.batch_size = batch_size or num_envs
         if num_envs % self.batch_size:
             raise ValueError("batch_size must divide num_envs")
@@ -307,11 +324,20 @@ class VecEnv:
         # savestate bank: the pool's states in slots [0, pool_size), bank_slots free ones after them
         self.pool_size = 0
         self._slots = self._pool_gen = None
-        if state_pool is not None or bank_slots:
+        self.fork_slots = int(fork_slots)
+        self._cap_lg = _seen_cap_log2(getattr(emulator, "max_episode_steps", 20480))
+        self._fork0 = 0             # first scratch slot of fork()
+        self._ck_return = self._ck_length = self._ck_slots = self._ck_valid = None
+        if bank_episodes and not getattr(emulator, "reward", False):
+            raise ValueError("bank_episodes=True needs the reward stack (reward=True)")
+        if self.fork_slots and not bank_episodes:
+            raise ValueError("fork_slots needs bank_episodes=True")
+        if state_pool is not None or bank_slots or self.fork_slots:
             pool = [st if isinstance(st, (bytes, bytearray)) else _read(st) for st in (state_pool or [])]
             if state_pool is not None and not pool:
                 raise ValueError("state_pool is empty")
-            self.emu.bank_create(len(pool) + int(bank_slots))
+            self._fork0 = len(pool) + int(bank_slots)
+            self.emu.bank_create(self._fork0 + self.fork_slots)
             for k, st in enumerate(pool):
                 self.emu.bank_put(k, st)
             self.pool_size = len(pool)
@@ -320,6 +346,19 @@ class VecEnv:
                 self._pool_gen.manual_seed(int(pool_seed))
                 # slot each emulator env last started from; padding envs keep -1 (the template)
                 self._slots = torch.full((n_phys,), -1, dtype=torch.int32, device=self.device)
+            if bank_episodes:
+                # what this class keeps per env of an episode, per slot: taken at a checkpoint,
+                # restored at a resume (device tensors, no host copy)
+                self.emu.bank_enable_episodes()
+                # (one entry past the last slot takes the writes of out-of-range slots, which the
+                # device rejects; _ck_valid mirrors the device's "holds an episode" flag)
+                k = self._fork0 + self.fork_slots + 1
+                self._ck_return = torch.zeros(k, dtype=torch.float64, device=self.device)
+                self._ck_length = torch.zeros(k, dtype=torch.float64, device=self.device)
+                self._ck_slots = torch.full((k,), -1, dtype=torch.int32, device=self.device)
+                self._ck_valid = torch.zeros(k, dtype=torch.bool, device=self.device)
+        elif bank_episodes:
+            raise ValueError("bank_episodes=True needs a bank: state_pool, bank_slots or fork_slots")
 
     def _draw_slots(self, psl: slice, done: torch.Tensor | None = None):
         """Draw a pool slot for the envs of emulator range psl (those with done[e] != 0) on the
@@ -364,6 +403,10 @@ class VecEnv:
                 raise ValueError("save_to_bank: a slot is named twice")
         self._join_streams()
         self.emu.bank_save(self._bank_map(envs, slots))
+        if self._ck_return is not None:     # a plain save leaves the slot without an episode
+            last = self._ck_return.numel() - 1
+            s = torch.as_tensor(slots, device=self.device).reshape(-1).long()
+            self._ck_valid[torch.where((s >= 0) & (s < last), s, last)] = False
 
     def load_from_bank(self, envs, slots):
         """Load bank slot slots[i] into env envs[i] (pk_bank_load: machine state only, the episode's
@@ -372,6 +415,80 @@ class VecEnv:
         emu.bank_rejects()."""
         self._join_streams()
         self.emu.bank_load(self._bank_map(envs, slots))
+
+    def _episode_args(self, envs, slots):
+        if self._ck_return is None:
+            raise RuntimeError("VecEnv(bank_episodes=True) keeps episode checkpoints")
+        envs = torch.as_tensor(envs, device=self.device).reshape(-1).long()
+        slots = torch.as_tensor(slots, device=self.device).reshape(-1).long()
+        if envs.numel() != slots.numel():
+            raise ValueError("envs and slots must have the same length")
+        return envs, slots
+
+    def checkpoint_to_bank(self, envs, slots, check: bool = True):
+        """Checkpoint the episode of env envs[i] into bank slot slots[i] (pk_bank_checkpoint): the
+        machine state as save_to_bank stores it, the episode's step counter and reward bookkeeping,
+        and this class's episode return / length and start slot of the env.  On the current stream
+        after a pipeline join, like save_to_bank; check=True rejects a slot named twice (host sync)."""
+        envs, slots = self._episode_args(envs, slots)
+        if check and torch.unique(slots).numel() != slots.numel():
+            raise ValueError("checkpoint_to_bank: a slot is named twice")
+        self._join_streams()
+        self.emu.bank_checkpoint(self._bank_map(envs, slots))
+        last = self._ck_return.numel() - 1
+        slots = torch.where((slots >= 0) & (slots < last), slots, last)
+        self._ck_return[slots] = self.stats.ep_return[envs]
+        self._ck_length[slots] = self.stats.ep_length[envs]
+        self._ck_valid[slots] = True
+        self._ck_valid[last] = False
+        if self._slots is not None:
+            self._ck_slots[slots] = self._slots[(envs // self.batch_size) * self.slot + envs % self.batch_size]
+
+    def resume_from_bank(self, envs, slots):
+        """Env envs[i] continues the episode checkpointed in slot slots[i] (pk_bank_resume): fed the
+        same actions it returns what the checkpointed env returned, its observation row shows the
+        resumed state at once, and its episode return / length and start slot are the checkpoint's.
+        Many envs may name one slot.  On the current stream after a pipeline join.  A slot that is
+        empty, out of range or holds no episode (save_to_bank, the pool) leaves its env alone and
+        counts in emu.bank_rejects(); sticky_errors stay with the env."""
+        envs, slots = self._episode_args(envs, slots)
+        self._join_streams()
+        self.emu.bank_resume(self._bank_map(envs, slots))
+        last = self._ck_return.numel() - 1
+        slots = torch.where((slots >= 0) & (slots < last), slots, last)
+        ok = self._ck_valid[slots]           # the envs the device does not reject
+        self.stats.ep_return[envs] = torch.where(ok, self._ck_return[slots], self.stats.ep_return[envs])
+        self.stats.ep_length[envs] = torch.where(ok, self._ck_length[slots], self.stats.ep_length[envs])
+        if self._slots is not None:
+            phys = (envs // self.batch_size) * self.slot + envs % self.batch_size
+            self._slots[phys] = torch.where(ok, self._ck_slots[slots], self._slots[phys])
+
+    def fork(self, dst_envs, src_envs, check: bool = True):
+        """Copy the running episode of env src_envs[i] over env dst_envs[i]: every distinct source
+        is checkpointed into one of the fork_slots scratch slots and the destinations resume from
+        those, on the current stream after a pipeline join.  The arguments are host lists (or
+        tensors, read back).  A destination named twice, or more distinct sources than fork_slots,
+        raises; check=True also rejects a destination that is a source of the same call."""
+        dst = [int(e) for e in torch.as_tensor(dst_envs).reshape(-1).tolist()]
+        src = [int(e) for e in torch.as_tensor(src_envs).reshape(-1).tolist()]
+        if self._ck_return is None:
+            raise RuntimeError("VecEnv(bank_episodes=True, fork_slots=...) forks envs")
+        if len(dst) != len(src):
+            raise ValueError("fork: dst_envs and src_envs must have the same length")
+        if any(not 0 <= e < self.num_envs for e in dst + src):
+            raise ValueError("fork: env index out of range")
+        if len(set(dst)) != len(dst):
+            raise ValueError("fork: a destination is named twice")
+        if check and set(dst) & set(src):
+            raise ValueError("fork: a destination is also a source")
+        uniq = sorted(set(src))
+        if len(uniq) > self.fork_slots:
+            raise ValueError(f"fork: {len(uniq)} distinct sources, {self.fork_slots} scratch slots (fork_slots)")
+        if not dst:
+            return
+        slot_of = {e: self._fork0 + k for k, e in enumerate(uniq)}
+        self.checkpoint_to_bank(uniq, [slot_of[e] for e in uniq], check=False)
+        self.resume_from_bank(dst, [slot_of[e] for e in src])
 
     def _range(self, b: int) -> slice:
         return slice(b * self.batch_size, (b + 1) * self.batch_size)
@@ -403,7 +520,11 @@ class VecEnv:
         if max_episode_steps is not None or reward_scale is not None:
             mes = max_episode_steps if max_episode_steps is not None else getattr(self.emu, "max_episode_steps", 20480)
             rsc = reward_scale if reward_scale is not None else getattr(self.emu, "reward_scale", 4.0)
+            grows = _seen_cap_log2(mes) > self._cap_lg      # the seen set never shrinks
+            self._cap_lg = max(self._cap_lg, _seen_cap_log2(mes))
             self.emu.set_episode_params(mes, rsc)
+            if grows and self._ck_return is not None:   # the device emptied every slot's episode part
+                self._ck_valid.zero_()
         if self._slots is None:
             obs = self._logical(self.emu.reset())
         else:
