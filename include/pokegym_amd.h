@@ -31,6 +31,8 @@
  *   pk_reset_from    reset from a state of the pool    environment.py:116, :122, :1241-1242
  *   pk_bank_checkpoint / pk_bank_resume   no reference equivalent: a whole episode (machine state
  *                    and the Environment's per-episode attributes) saved to and continued from a slot
+ *   pk_archive_update / pk_archive_explore   no reference equivalent: the best episode per cell key,
+ *                    kept in bank slots, and envs resumed from cells drawn by visit count
  * With PK_F_REWARD, pk_step also runs the reward stack of Environment.step
  * (environment.py:1338-1612) and pk_reset follows Environment.reset (:1233-1334).
  */
@@ -43,7 +45,7 @@
 extern "C" {
 #endif
 
-#define PK_ABI_VERSION 8
+#define PK_ABI_VERSION 9
 #define PK_STATE_V9_BYTES 142610u
 #define PK_SCREEN_ROWS 144u
 #define PK_SCREEN_COLS 160u
@@ -261,6 +263,73 @@ int pk_bank_resume(pk_handle* h, const int32_t* slot_of_env_dev, uint32_t env0, 
 /* Envs rejected by pk_bank_save / pk_bank_load / pk_reset_from / pk_bank_checkpoint /
  * pk_bank_resume since the last call; clears the counter (synchronous). */
 int pk_bank_rejects(pk_handle* h, uint64_t* out);
+
+/* Exploration archive (Go-Explore cells) on the bank: a map from 64-bit cell keys to bank slots
+ * that keeps the best episode seen per cell, lives on the device and is driven without a host
+ * sync.  Cell c owns bank slot slot0 + c for the life of the handle.  An archive holds, per cell,
+ * key, score, length (the winner's step counter), visits and picks, and besides the cells in use,
+ * an overflow count and the number of explore calls made.
+ *
+ * pk_archive_create (synchronous): once per handle; needs a bank with episode parts
+ * (pk_bank_enable_episodes), n_cells in 1..65536 and slot0 + n_cells <= pk_bank_slots; seed seeds
+ * the draws.  On failure (no episode parts, second call, bad range, out of memory) the handle is
+ * unchanged.  pk_archive_cells: n_cells, 0 without an archive.  Every other archive call on a
+ * handle without one fails with a negative code and does nothing.  Memory: 76 to 100 bytes per cell,
+ * and per env of the handle 81 to 153 bytes of per-call words (the tables are powers of two).
+ *
+ * pk_cell_keys (any handle; no archive, no PK_F_REWARD needed): for each env of the range
+ *   keys[e] = map | (x >> shift) << 8 | (y >> shift) << 16 | badges << 24
+ * with map = guest 0xD35E, x = 0xD362, y = 0xD361, badges = 0xD356; shift in 0..7.  keys_dev is a
+ * full-size device u64[n]; only [env0, env0 + count) is written.
+ *
+ * pk_archive_update: keys_dev u64[n], scores_dev f64[n], mask_dev u8[n] or NULL (= every env), full
+ * size and indexed by env; the range follows pk_step_range's rule.  An env takes no part when its
+ * mask byte is 0, its key is UINT64_MAX (reserved: "no cell") or its score is NaN.  The result is
+ * the one of walking the envs that take part in ascending env index:
+ *   - an env whose key has no cell gets the next free cell (visits = picks = 0, no record); when
+ *     all n_cells are in use, overflow rises by one and the env does nothing more;
+ *   - visits of the cell rises by one;
+ *   - the env becomes the cell's record (score, length = its step counter) and the call's winner
+ *     of the cell when the cell has no record, its score is greater, or its score is equal and
+ *     its length less.  Scores compare as IEEE doubles.
+ * So ties inside a call go to the lowest env, a stored record only yields to a strictly better
+ * one, and new cells are numbered by the lowest env that reaches them, which also decides who
+ * finds the archive full.  Every winner is then checkpointed into its cell's slot exactly as
+ * pk_bank_checkpoint does it, at this point of the stream: the record and the slot never disagree.
+ * slot_of_env_out_dev (optional device i32[n]) receives, over the range only, slot0 + c for the
+ * winner of cell c and -1 for every other env.
+ *
+ * pk_archive_explore: every env of the range with mask_dev[e] != 0 (NULL = all) draws a cell and
+ * resumes the episode in its slot exactly as pk_bank_resume does it (observation rebuilt).  With
+ * the cells in use 0..used-1, their weights taken at the start of the call
+ *   w(c) = 2^32 div isqrt((visits[c] + picks[c] + 1) << 16)          (integers)
+ * P their inclusive prefix sums (u64) and T the total, env e draws
+ *   r = mix(seed + 0x9E3779B97F4A7C15 * ((draw_calls << 32) + e + 1)) mod T     (mod 2^64 inside)
+ * where mix is splitmix64's finaliser (z ^= z >> 30, z *= 0xBF58476D1CE4E5B9, z ^= z >> 27,
+ * z *= 0x94D049BB133111EB, z ^= z >> 31), and takes the first c with P[c] > r.  After all draws
+ * picks[c] has risen by the envs that drew c and draw_calls by one (per call, whatever its range):
+ * all draws of a call see one distribution.  With an empty archive every masked env is a reject:
+ * untouched, and counted in the bank's reject counter.  slot_of_env_out_dev (optional) receives
+ * the slot each env resumed from, -1 for envs that took no part or were rejected (a cell whose
+ * slot lost its episode part — pk_bank_put, pk_bank_save, a grown seen set — rejects like that).
+ *
+ * pk_archive_read (synchronous): host arrays of n_cells elements each, any pointer may be NULL;
+ * elements from *used on are keys UINT64_MAX and zeros.  *overflow is not cleared by reading.
+ *
+ * Ordering: archive calls are stream-ordered and never sync the host.  The archive is one shared
+ * structure: the caller orders the calls that touch it, as it orders bank calls that touch one
+ * slot; calls over different ranges are allowed, but not concurrently.  Everything observable —
+ * cell numbers, records, counters, draws, slot contents — is the same from run to run; only the
+ * places of keys inside the hash tables depend on timing. */
+int pk_archive_create(pk_handle* h, uint32_t slot0, uint32_t n_cells, uint64_t seed);
+uint32_t pk_archive_cells(const pk_handle* h);
+int pk_cell_keys(pk_handle* h, uint32_t shift, uint64_t* keys_dev, uint32_t env0, uint32_t count, void* stream);
+int pk_archive_update(pk_handle* h, const uint64_t* keys_dev, const double* scores_dev, const uint8_t* mask_dev,
+                      uint32_t env0, uint32_t count, int32_t* slot_of_env_out_dev, void* stream);
+int pk_archive_explore(pk_handle* h, const uint8_t* mask_dev, uint32_t env0, uint32_t count,
+                       int32_t* slot_of_env_out_dev, void* stream);
+int pk_archive_read(pk_handle* h, uint32_t* used, uint64_t* keys, double* scores, uint32_t* lengths,
+                    uint32_t* visits, uint32_t* picks, uint64_t* overflow);
 
 /* Emulated instructions executed by the last pk_step, summed over envs (synchronous). */
 int pk_last_instr_count(pk_handle* h, uint64_t* out);

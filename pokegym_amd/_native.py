@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # PK_LIB selects an alternative in-tree build (A/B kernel experiments); default: lib/libpokegym_amd.so
 LIB_PATH = os.environ.get("PK_LIB") or os.path.join(HERE, "lib", "libpokegym_amd.so")
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 PK_F_RENDER = 1
 PK_F_REWARD = 2
 PK_F_RELOAD_ON_RESET = 4
@@ -34,7 +34,9 @@ EXPORTS = ("pk_create", "pk_destroy", "pk_last_error", "pk_abi_version", "pk_res
            "pk_set_episode_params", "pk_launch_shape",
            "pk_bank_create", "pk_bank_slots", "pk_bank_put", "pk_bank_get", "pk_bank_save", "pk_bank_load",
            "pk_reset_from", "pk_bank_rejects",
-           "pk_bank_enable_episodes", "pk_bank_has_episodes", "pk_bank_checkpoint", "pk_bank_resume")
+           "pk_bank_enable_episodes", "pk_bank_has_episodes", "pk_bank_checkpoint", "pk_bank_resume",
+           "pk_archive_create", "pk_archive_cells", "pk_cell_keys", "pk_archive_update", "pk_archive_explore",
+           "pk_archive_read")
 
 
 class PkConfig(ctypes.Structure):
@@ -103,6 +105,7 @@ def bind(L):
     bind_v2(L)
     bind_v7(L)
     bind_v8(L)
+    bind_v9(L)
 
 
 def bind_v2(L):
@@ -154,6 +157,19 @@ def bind_v8(L):
     L.pk_bank_has_episodes.argtypes = [vp]
     L.pk_bank_checkpoint.argtypes = [vp, vp, u32, u32, vp]
     L.pk_bank_resume.argtypes = [vp, vp, u32, u32, vp]
+
+
+def bind_v9(L):
+    """argtypes of the exploration archive (ABI v9; shared with the host-simulation test build)."""
+    vp = ctypes.c_void_p
+    u32 = ctypes.c_uint32
+    L.pk_archive_create.argtypes = [vp, u32, u32, ctypes.c_uint64]
+    L.pk_archive_cells.argtypes = [vp]
+    L.pk_archive_cells.restype = u32
+    L.pk_cell_keys.argtypes = [vp, u32, vp, u32, u32, vp]
+    L.pk_archive_update.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp]
+    L.pk_archive_explore.argtypes = [vp, vp, u32, u32, vp, vp]
+    L.pk_archive_read.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
 
 
 def check(rc: int, what: str):

@@ -42,6 +42,11 @@ hipError_t pk_launch_ram_copy(uint8_t* mem, uint8_t* dense, uint32_t n, uint32_t
 hipError_t pk_launch_bank_list(const PkBankArgs& a, hipStream_t s);
 hipError_t pk_launch_bank_copy(const PkBankArgs& a, hipStream_t s);
 hipError_t pk_launch_ep_move(const PkEpArgs& a, hipStream_t s);
+hipError_t pk_launch_arch_update(const PkArchArgs& a, hipStream_t s);
+hipError_t pk_launch_arch_draw(const PkArchArgs& a, hipStream_t s);
+hipError_t pk_launch_arch_out(const PkArchArgs& a, hipStream_t s);
+hipError_t pk_launch_cell_keys(const uint8_t* mem, uint32_t sh, uint32_t shift, uint64_t* keys, uint32_t env0,
+                               uint32_t env1, hipStream_t s);
 
 namespace {
 
@@ -291,6 +296,14 @@ struct pk_handle {
     uint32_t* e_mask = nullptr;
     uint32_t* e_cutc = nullptr;
     uint8_t* b_ep_filled = nullptr;
+    // exploration archive (pk_archive_create; pk_layout.h PkArchArgs), arch_cells = 0 without one:
+    // the persistent part, and the per-call words of an update in two blocks, one cleared to all
+    // ones (empty keys, the min words) and one to zero (the max words, the counts)
+    uint32_t arch_cells = 0, arch_slot0 = 0, arch_imask = 0;
+    uint64_t arch_seed = 0;
+    uint8_t* a_fix = nullptr;
+    uint8_t* a_ones = nullptr;
+    uint8_t* a_zero = nullptr;
     // profiling: 4 events per profiled step (start, after K1, after K2, after K4+K3)
     bool prof = false;
     std::vector<hipEvent_t> ev_pool;
@@ -331,7 +344,7 @@ void pk_destroy(pk_handle* h) {
                     h->t_lat, h->t_screen, h->scratch, h->rs, h->rsd, h->seen, h->mask, h->cutc, h->obs, h->reload,
                     h->lists, h->dbg, h->info, h->info_flag, h->heat, h->info_bits, h->bank_slot_s, h->slot_bank_s,
                     h->b_mem, h->b_regs, h->b_lat, h->b_screen, h->b_filled, h->b_rejects, h->b_lists, h->b_src,
-                    h->e_fields, h->e_seen, h->e_mask, h->e_cutc, h->b_ep_filled};
+                    h->e_fields, h->e_seen, h->e_mask, h->e_cutc, h->b_ep_filled, h->a_fix, h->a_ones, h->a_zero};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     delete h;
@@ -1331,6 +1344,158 @@ int pk_bank_rejects(pk_handle* h, uint64_t* out) {
     HIPCHK(hipMemcpy(&v, h->b_rejects, 4, hipMemcpyDeviceToHost));
     HIPCHK(hipMemset(h->b_rejects, 0, 4));
     *out = v;
+    return 0;
+}
+
+// ---- exploration archive on the bank -----------------------------------------------------------
+
+static uint32_t pow2_at_least(uint64_t v) {
+    uint32_t p = 64;
+    while (p < v) p <<= 1;
+    return p;
+}
+
+// the persistent block: [hdr | a_key | a_score | prefix | i_key] u64, [a_len | a_visits | a_picks |
+// i_cell | tgt | map] u32, [flag] u8
+static size_t arch_fix_bytes(uint32_t cells, uint32_t isize, uint32_t npad) {
+    return ((size_t)PK_AH_WORDS + 3ull * cells + isize) * 8 + (3ull * cells + isize + 2ull * npad) * 4 + npad;
+}
+
+// the argument block of an archive call over [env0, env1): the per-call blocks are carved for a
+// scratch table of ssize entries
+static PkArchArgs arch_args(pk_handle* h, uint32_t env0, uint32_t env1, uint32_t ssize) {
+    PkArchArgs a;
+    memset(&a, 0, sizeof a);
+    const uint32_t K = h->arch_cells, I = h->arch_imask + 1u;
+    uint64_t* q = (uint64_t*)h->a_fix;
+    a.hdr = q; q += PK_AH_WORDS;
+    a.a_key = q; q += K;
+    a.a_score = (double*)q; q += K;
+    a.prefix = q; q += K;
+    a.i_key = q; q += I;
+    uint32_t* w = (uint32_t*)q;
+    a.a_len = w; w += K;
+    a.a_visits = w; w += K;
+    a.a_picks = w; w += K;
+    a.i_cell = w; w += I;
+    a.tgt = w; w += h->npad;
+    a.map = (int32_t*)w; w += h->npad;
+    a.flag = (uint8_t*)w;
+    q = (uint64_t*)h->a_ones;
+    a.c_le = q; q += K;
+    a.s_key = q; q += ssize;
+    a.s_le = q; q += ssize;
+    a.s_first = (uint32_t*)q;
+    q = (uint64_t*)h->a_zero;
+    a.c_max = q; q += K;
+    a.s_max = q; q += ssize;
+    a.s_cnt = (uint32_t*)q;
+    a.s_cell = a.s_cnt + ssize;
+    a.time_reg = h->regs + (size_t)PK_R_TIME * h->npad;
+    a.b_rejects = h->b_rejects;
+    a.src = h->b_src;
+    a.seed = h->arch_seed;
+    a.i_mask = h->arch_imask; a.s_mask = ssize - 1u;
+    a.n_cells = K; a.slot0 = h->arch_slot0;
+    a.env0 = env0; a.env1 = env1;
+    return a;
+}
+
+uint32_t pk_archive_cells(const pk_handle* h) { return h ? h->arch_cells : 0; }
+
+int pk_archive_create(pk_handle* h, uint32_t slot0, uint32_t n_cells, uint64_t seed) {
+    if (!h) return fail(-EINVAL, "null handle");
+    if (h->arch_cells) return fail(-EEXIST, "the handle already has an archive of %u cells", h->arch_cells);
+    if (!h->bank_n || !h->b_ep_filled)
+        return fail(-ENOENT, "an archive needs a bank with episode parts (pk_bank_create, pk_bank_enable_episodes)");
+    if (n_cells == 0 || n_cells > PK_ARCH_MAX_CELLS || (uint64_t)slot0 + n_cells > h->bank_n)
+        return fail(-EINVAL, "cells [%u, +%u): n_cells must be 1..%u and the slots inside the bank's %u", slot0, n_cells,
+                    PK_ARCH_MAX_CELLS, h->bank_n);
+    HIPCHK(hipSetDevice(h->device));
+    const uint32_t I = pow2_at_least(2ull * n_cells), S = pow2_at_least(2ull * h->npad);
+    const size_t fix = arch_fix_bytes(n_cells, I, h->npad);
+    const size_t ones = ((size_t)n_cells + 2ull * S) * 8 + (size_t)S * 4, zero = ((size_t)n_cells + S) * 8 + 2ull * S * 4;
+    uint8_t *pf = nullptr, *po = nullptr, *pz = nullptr;
+    hipError_t e = hipMalloc((void**)&pf, fix);
+    if (e == hipSuccess) e = hipMalloc((void**)&po, ones);
+    if (e == hipSuccess) e = hipMalloc((void**)&pz, zero);
+    if (e == hipSuccess) e = hipMemset(pf, 0, fix);
+    // no cell has a key yet, the index is empty
+    if (e == hipSuccess) e = hipMemset(pf + PK_AH_WORDS * 8, 0xFF, (size_t)n_cells * 8);
+    if (e == hipSuccess) e = hipMemset(pf + ((size_t)PK_AH_WORDS + 3ull * n_cells) * 8, 0xFF, (size_t)I * 8);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        void* ptrs[] = {pf, po, pz};
+        for (void* p : ptrs)
+            if (p) (void)hipFree(p);
+        (void)hipGetLastError();
+        return fail(-ENOMEM, "archive of %u cells (%zu bytes): %s", n_cells, fix + ones + zero, hipGetErrorString(e));
+    }
+    h->a_fix = pf; h->a_ones = po; h->a_zero = pz;
+    h->arch_cells = n_cells; h->arch_slot0 = slot0; h->arch_imask = I - 1u; h->arch_seed = seed;
+    return 0;
+}
+
+int pk_cell_keys(pk_handle* h, uint32_t shift, uint64_t* keys, uint32_t env0, uint32_t count, void* stream) {
+    int rc;
+    if ((rc = check_range(h, env0, count))) return rc;
+    if (!keys) return fail(-EINVAL, "keys_dev is required");
+    if (shift > 7) return fail(-EINVAL, "shift must be 0..7");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(pk_launch_cell_keys(h->mem, h->ilv_sh, shift, keys, env0, env0 + count, (hipStream_t)stream));
+    return 0;
+}
+
+int pk_archive_update(pk_handle* h, const uint64_t* keys, const double* scores, const uint8_t* mask, uint32_t env0,
+                      uint32_t count, int32_t* slot_out, void* stream) {
+    int rc;
+    if ((rc = check_range(h, env0, count))) return rc;
+    if (!h->arch_cells) return fail(-ENOENT, "the handle has no archive (pk_archive_create)");
+    if (!keys || !scores) return fail(-EINVAL, "keys_dev and scores_dev are required");
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    const uint32_t S = pow2_at_least(2ull * count);
+    PkArchArgs a = arch_args(h, env0, env0 + count, S);
+    a.keys = keys; a.scores = scores; a.mask = mask; a.out = slot_out;
+    HIPCHK(hipMemsetAsync(h->a_ones, 0xFF, ((size_t)a.n_cells + 2ull * S) * 8 + (size_t)S * 4, s));
+    HIPCHK(hipMemsetAsync(h->a_zero, 0, ((size_t)a.n_cells + S) * 8 + (size_t)S * 4, s));
+    HIPCHK(pk_launch_arch_update(a, s));
+    if ((rc = episode_move(h, PK_BANK_SAVE, a.map, env0, count, stream))) return rc;
+    if (slot_out) HIPCHK(pk_launch_arch_out(a, s));
+    return 0;
+}
+
+int pk_archive_explore(pk_handle* h, const uint8_t* mask, uint32_t env0, uint32_t count, int32_t* slot_out, void* stream) {
+    int rc;
+    if ((rc = check_range(h, env0, count))) return rc;
+    if (!h->arch_cells) return fail(-ENOENT, "the handle has no archive (pk_archive_create)");
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    PkArchArgs a = arch_args(h, env0, env0 + count, 64);
+    a.mask = mask; a.out = slot_out;
+    HIPCHK(pk_launch_arch_draw(a, s));
+    if ((rc = episode_move(h, PK_BANK_LOAD, a.map, env0, count, stream))) return rc;
+    if (slot_out) HIPCHK(pk_launch_arch_out(a, s));
+    return 0;
+}
+
+int pk_archive_read(pk_handle* h, uint32_t* used, uint64_t* keys, double* scores, uint32_t* lengths, uint32_t* visits,
+                    uint32_t* picks, uint64_t* overflow) {
+    if (!h) return fail(-EINVAL, "null handle");
+    if (!h->arch_cells) return fail(-ENOENT, "the handle has no archive (pk_archive_create)");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipDeviceSynchronize());
+    const PkArchArgs a = arch_args(h, 0, 0, 64);
+    const size_t K = a.n_cells;
+    uint64_t hdr[PK_AH_WORDS];
+    HIPCHK(hipMemcpy(hdr, a.hdr, sizeof hdr, hipMemcpyDeviceToHost));
+    if (used) *used = (uint32_t)hdr[PK_AH_USED];
+    if (overflow) *overflow = hdr[PK_AH_OVERFLOW];
+    if (keys) HIPCHK(hipMemcpy(keys, a.a_key, K * 8, hipMemcpyDeviceToHost));
+    if (scores) HIPCHK(hipMemcpy(scores, a.a_score, K * 8, hipMemcpyDeviceToHost));
+    if (lengths) HIPCHK(hipMemcpy(lengths, a.a_len, K * 4, hipMemcpyDeviceToHost));
+    if (visits) HIPCHK(hipMemcpy(visits, a.a_visits, K * 4, hipMemcpyDeviceToHost));
+    if (picks) HIPCHK(hipMemcpy(picks, a.a_picks, K * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -11,7 +11,9 @@
 //
 // Everything here is integer byte work; no MFMA.
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "pk_layout.h"
 #include "pk_render.h"
@@ -375,5 +377,367 @@ hipError_t pk_launch_bank_copy(const PkBankArgs& a, hipStream_t s) {
     if (e != hipSuccess) return e;
     const u32 sgrid = (count * 16u + 255u) / 256u;
     hipLaunchKernelGGL(pk_bank_state_kernel, dim3(sgrid < 4096u ? sgrid : 4096u), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// Exploration archive (pk_archive_update / pk_archive_explore / pk_cell_keys): cells of the best
+// episode per key, kept next to the bank.  The result of an update is the one of walking the envs
+// in ascending order (include/pokegym_amd.h states the model); the kernels reach it without any
+// order among threads: integer adds, 64-bit max / min on order-preserving words and a scan.  The
+// phases are separate launches, so no kernel waits for another thread or workgroup, and every
+// probe loop ends after one pass over its table at the latest (the tables are at most half full).
+typedef uint64_t u64;
+typedef unsigned long long ull;
+
+#ifndef __HIPCC__
+// host versions for the host-simulation build, whose shim has the 32-bit atomicAdd only.  Its
+// "wave" is one lane (the ballot is this lane's bit 0), so a shuffle returns the lane's own value.
+static inline ull atomicAdd(ull* p, ull v) { return __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
+static inline ull atomicCAS(ull* p, ull cmp, ull v) {
+    __atomic_compare_exchange_n(p, &cmp, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED);
+    return cmp;
+}
+static inline ull atomicMax(ull* p, ull v) {
+    ull old = __atomic_load_n(p, __ATOMIC_RELAXED);
+    while (old < v && !__atomic_compare_exchange_n(p, &old, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+    return old;
+}
+static inline ull atomicMin(ull* p, ull v) {
+    ull old = __atomic_load_n(p, __ATOMIC_RELAXED);
+    while (old > v && !__atomic_compare_exchange_n(p, &old, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+    return old;
+}
+static inline u32 atomicMin(u32* p, u32 v) {
+    u32 old = __atomic_load_n(p, __ATOMIC_RELAXED);
+    while (old > v && !__atomic_compare_exchange_n(p, &old, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+    return old;
+}
+static inline u32 __shfl(u32 v, int) { return v; }
+static inline ull __shfl_xor(ull v, int) { return v; }
+static inline u32 pk_lane() { return 0u; }
+#else
+__device__ static inline u32 pk_lane() { return threadIdx.x & 63u; }
+#endif
+
+// IEEE order of non-NaN doubles as unsigned order, -0.0 and +0.0 the same word; never 0
+__device__ static inline u64 pk_arch_enc(double d) {
+    d += 0.0;
+    u64 b;
+    memcpy(&b, &d, 8);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
+__device__ static inline u64 pk_arch_mix(u64 z) {   // splitmix64's finaliser
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// One round of the wave pre-reduction: the pending lanes (todo) that share the target of the first
+// pending lane form a group (match, its lanes mm); lead marks that first lane, which is the
+// group's lowest env.  False when no lane is pending.  Every lane of the wave calls it.
+__device__ static inline bool pk_arch_group(bool todo, u32 t, bool& match, bool& lead, u64& mm) {
+    const u64 m = __builtin_amdgcn_ballot_w64(todo);
+    if (!m) return false;
+    const u32 leader = (u32)__builtin_ffsll((long long)m) - 1u;
+    const u32 lt = __shfl(t, (int)leader);
+    match = todo && t == lt;
+    mm = __builtin_amdgcn_ballot_w64(match);
+    lead = pk_lane() == leader;
+    return true;
+}
+
+// the words an env brings to an update: whether it takes part, its encoded score and length << 32 | env
+__device__ static inline bool pk_arch_env(const PkArchArgs& A, u32 e, u64& key, u64& enc, u64& le) {
+    if (e >= A.env1 || (A.mask && !A.mask[e])) return false;
+    key = A.keys[e];
+    const double sc = A.scores[e];
+    if (key == PK_ARCH_NOKEY || sc != sc) return false;
+    enc = pk_arch_enc(sc);
+    le = ((u64)A.time_reg[e] << 32) | e;
+    return true;
+}
+
+// phase 1, thread = env: find the key's cell in the index, else claim a scratch entry for it; count
+// the visit, and bring the score to the target's max word — for a known cell only where it beats
+// the stored record (a better score, or the same score in fewer steps)
+__global__ void __launch_bounds__(256) pk_arch_claim_kernel(PkArchArgs A) {
+    const u32 e = A.env0 + blockIdx.x * blockDim.x + threadIdx.x;
+    u64 key = PK_ARCH_NOKEY, enc = 0, le = 0;
+    u32 t = PK_ARCH_NONE;
+    bool cand = false;
+    if (pk_arch_env(A, e, key, enc, le)) {
+        const u32 h = (u32)pk_arch_mix(key);
+        u32 pos = h & A.i_mask;
+        for (u32 p = 0; p <= A.i_mask; p++, pos = (pos + 1u) & A.i_mask) {
+            const u64 k = A.i_key[pos];
+            if (k == key) t = A.i_cell[pos];
+            if (k == key || k == PK_ARCH_NOKEY) break;
+        }
+        if (t != PK_ARCH_NONE) {
+            const u64 renc = pk_arch_enc(A.a_score[t]);
+            cand = enc > renc || (enc == renc && (u32)(le >> 32) < A.a_len[t]);
+        } else {
+            pos = h & A.s_mask;
+            for (u32 p = 0; p <= A.s_mask; p++, pos = (pos + 1u) & A.s_mask) {
+                ull* sk = reinterpret_cast<ull*>(A.s_key + pos);
+                u64 k = *sk;
+                if (k == PK_ARCH_NOKEY) k = atomicCAS(sk, (ull)PK_ARCH_NOKEY, (ull)key);
+                if (k == PK_ARCH_NOKEY || k == key) {
+                    t = A.n_cells + pos;
+                    cand = true;
+                    break;
+                }
+            }
+        }
+    }
+    if (e < A.env1) A.tgt[e] = t;
+    bool todo = t != PK_ARCH_NONE, match, lead;
+    u64 mm;
+    for (u32 it = 0; it <= PK_ARCH_PRE; it++) {
+        u32 n = 1;
+        u64 best = cand ? enc : 0;
+        if (it < PK_ARCH_PRE) {   // a group per round; after the last round every lane goes alone
+            if (!pk_arch_group(todo, t, match, lead, mm)) break;
+            best = match ? best : 0;
+            for (int o = 32; o; o >>= 1) {
+                const u64 other = __shfl_xor((ull)best, o);
+                best = other > best ? other : best;
+            }
+            n = (u32)__builtin_popcountll(mm);
+        } else {
+            match = lead = todo;
+        }
+        if (lead && match) {
+            if (t < A.n_cells) {
+                atomicAdd(A.a_visits + t, n);
+                if (best) atomicMax(reinterpret_cast<ull*>(A.c_max + t), (ull)best);
+            } else {
+                const u32 j = t - A.n_cells;
+                atomicAdd(A.s_cnt + j, n);
+                atomicMax(reinterpret_cast<ull*>(A.s_max + j), (ull)best);
+                atomicMin(A.s_first + j, e);
+            }
+        }
+        todo = todo && !match;
+    }
+}
+
+// phase 2, thread = env: among the envs that hold the target's best score, the least length, then
+// the least env; and flag the env that is the first of a new key
+__global__ void __launch_bounds__(256) pk_arch_best_kernel(PkArchArgs A) {
+    const u32 e = A.env0 + blockIdx.x * blockDim.x + threadIdx.x;
+    u64 key, enc = 0, le = 0;
+    const u32 t = e < A.env1 ? A.tgt[e] : PK_ARCH_NONE;
+    bool todo = false, match, lead;
+    if (t != PK_ARCH_NONE) {
+        pk_arch_env(A, e, key, enc, le);
+        const u32 j = t - A.n_cells;
+        todo = enc == (t < A.n_cells ? A.c_max[t] : A.s_max[j]);
+        A.flag[e] = t >= A.n_cells && A.s_first[j] == e ? 1 : 0;
+    } else if (e < A.env1) {
+        A.flag[e] = 0;
+    }
+    u64 mm;
+    for (u32 it = 0; it <= PK_ARCH_PRE; it++) {
+        u64 least = le;
+        if (it < PK_ARCH_PRE) {
+            if (!pk_arch_group(todo, t, match, lead, mm)) break;
+            least = match ? least : ~0ull;
+            for (int o = 32; o; o >>= 1) {
+                const u64 other = __shfl_xor((ull)least, o);
+                least = other < least ? other : least;
+            }
+        } else {
+            match = lead = todo;
+        }
+        if (lead && match) atomicMin(reinterpret_cast<ull*>(t < A.n_cells ? A.c_le + t : A.s_le + (t - A.n_cells)), (ull)least);
+        todo = todo && !match;
+    }
+}
+
+// phase 3, one workgroup: number the new keys in the order of their first envs (a scan of the
+// flags), give them the free cells, and count the envs of the keys that found the archive full
+#define PK_K1_KERNEL_ARCH_RANK pk_arch_rank_kernel
+__global__ void __launch_bounds__(256) pk_arch_rank_kernel(PkArchArgs A) {
+    __shared__ u32 sums[256];
+    const u32 tid = threadIdx.x, count = A.env1 - A.env0, chunk = (count + 255u) / 256u;
+    const u32 b = A.env0 + (tid * chunk < count ? tid * chunk : count);
+    const u32 end = A.env1 - b < chunk ? A.env1 : b + chunk;
+    const u32 used0 = (u32)A.hdr[PK_AH_USED];
+    u32 s = 0;
+    for (u32 e = b; e < end; e++) s += A.flag[e];
+    sums[tid] = s;
+    __syncthreads();
+    for (u32 o = 1; o < 256u; o <<= 1) {
+        const u32 v = tid >= o ? sums[tid - o] : 0u;
+        __syncthreads();
+        sums[tid] += v;
+        __syncthreads();
+    }
+    u32 r = used0 + sums[tid] - s;
+    const u32 total = used0 + sums[255];
+    ull lost = 0;
+    for (u32 e = b; e < end; e++) {
+        if (!A.flag[e]) continue;
+        const u32 j = A.tgt[e] - A.n_cells;
+        if (r < A.n_cells) {
+            A.s_cell[j] = r;
+        } else {
+            A.s_cell[j] = PK_ARCH_NONE;
+            lost += A.s_cnt[j];
+        }
+        r++;
+    }
+    if (lost) atomicAdd(reinterpret_cast<ull*>(A.hdr + PK_AH_OVERFLOW), lost);
+    if (tid == 0) A.hdr[PK_AH_USED] = total < A.n_cells ? total : A.n_cells;
+}
+
+// phase 4, thread = env: the first env of an accepted new key writes the cell and enters the key
+// into the index; the winner of a target writes the record; every env gets its line of the slot map
+__global__ void __launch_bounds__(256) pk_arch_commit_kernel(PkArchArgs A) {
+    const u32 e = A.env0 + blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= A.env1) return;
+    const u32 t = A.tgt[e];
+    int32_t slot = -1;
+    u64 key, enc, le;
+    if (t != PK_ARCH_NONE) {
+        pk_arch_env(A, e, key, enc, le);
+        u32 c = t;
+        bool win;
+        if (t < A.n_cells) {
+            win = enc == A.c_max[t] && le == A.c_le[t];
+        } else {
+            const u32 j = t - A.n_cells;
+            c = A.s_cell[j];
+            win = c != PK_ARCH_NONE && enc == A.s_max[j] && le == A.s_le[j];
+            if (c != PK_ARCH_NONE && A.s_first[j] == e) {
+                A.a_key[c] = key;
+                A.a_visits[c] = A.s_cnt[j];
+                A.a_picks[c] = 0;
+                u32 pos = (u32)pk_arch_mix(key) & A.i_mask;
+                for (u32 p = 0; p <= A.i_mask; p++, pos = (pos + 1u) & A.i_mask) {
+                    ull* ik = reinterpret_cast<ull*>(A.i_key + pos);
+                    if (*ik != PK_ARCH_NOKEY) continue;
+                    if (atomicCAS(ik, (ull)PK_ARCH_NOKEY, (ull)key) == PK_ARCH_NOKEY) {
+                        A.i_cell[pos] = c;
+                        break;
+                    }
+                }
+            }
+        }
+        if (win) {
+            A.a_score[c] = A.scores[e];
+            A.a_len[c] = (u32)(le >> 32);
+            slot = (int32_t)(A.slot0 + c);
+        }
+    }
+    A.map[e] = slot;
+}
+
+// explore, one workgroup: the weights of the cells in use (Go-Explore's 1 / sqrt(n + 1) in fixed
+// point, integers only) and their inclusive prefix sums; the call takes its number
+#define PK_K1_KERNEL_ARCH_SCAN pk_arch_scan_kernel
+__device__ static inline u64 pk_arch_weight(u32 visits, u32 picks) {
+    const u64 x = ((u64)visits + picks + 1u) << 16;     // < 2^50: exact as a double
+    u64 r = (u64)sqrt((double)x);
+    if (r * r > x) r--;
+    if ((r + 1u) * (r + 1u) <= x) r++;
+    return (1ull << 32) / r;
+}
+__global__ void __launch_bounds__(256) pk_arch_scan_kernel(PkArchArgs A) {
+    __shared__ u64 sums[256];
+    const u32 tid = threadIdx.x, used = (u32)A.hdr[PK_AH_USED], chunk = (used + 255u) / 256u;
+    const u32 b = tid * chunk < used ? tid * chunk : used;
+    const u32 end = used - b < chunk ? used : b + chunk;
+    u64 s = 0;
+    for (u32 c = b; c < end; c++) s += pk_arch_weight(A.a_visits[c], A.a_picks[c]);
+    sums[tid] = s;
+    __syncthreads();
+    for (u32 o = 1; o < 256u; o <<= 1) {
+        const u64 v = tid >= o ? sums[tid - o] : 0u;
+        __syncthreads();
+        sums[tid] += v;
+        __syncthreads();
+    }
+    u64 run = sums[tid] - s;
+    for (u32 c = b; c < end; c++) {
+        run += pk_arch_weight(A.a_visits[c], A.a_picks[c]);
+        A.prefix[c] = run;
+    }
+    if (tid == 0) {
+        A.hdr[PK_AH_TOTAL] = sums[255];
+        A.hdr[PK_AH_CUR] = A.hdr[PK_AH_DRAWS];
+        A.hdr[PK_AH_DRAWS] += 1u;
+    }
+}
+
+// explore, thread = env: draw a cell by the prefix sums and count the pick.  The picks only enter
+// the weights of the next call's scan, so every draw of a call sees one distribution.
+__global__ void __launch_bounds__(256) pk_arch_draw_kernel(PkArchArgs A) {
+    const u32 e = A.env0 + blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= A.env1) return;
+    int32_t slot = -1;
+    if (!A.mask || A.mask[e]) {
+        const u32 used = (u32)A.hdr[PK_AH_USED];
+        if (!used) {
+            atomicAdd(A.b_rejects, 1u);
+        } else {
+            const u64 x = A.seed + 0x9E3779B97F4A7C15ull * ((A.hdr[PK_AH_CUR] << 32) + e + 1u);
+            const u64 r = pk_arch_mix(x) % A.hdr[PK_AH_TOTAL];
+            u32 lo = 0, hi = used - 1u;
+            for (u32 it = 0; it < 17u && lo < hi; it++) {   // used <= 2^16
+                const u32 mid = (lo + hi) >> 1;
+                if (A.prefix[mid] > r) hi = mid;
+                else lo = mid + 1u;
+            }
+            atomicAdd(A.a_picks + lo, 1u);
+            slot = (int32_t)(A.slot0 + lo);
+        }
+    }
+    A.map[e] = slot;
+}
+
+// the caller's slot_of_env_out: the slot the bank accepted for the env, -1 for every other env
+__global__ void __launch_bounds__(256) pk_arch_out_kernel(PkArchArgs A) {
+    const u32 e = A.env0 + blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < A.env1) A.out[e] = A.src[e];
+}
+
+// pk_cell_keys, thread = env: map | (x >> shift) << 8 | (y >> shift) << 16 | badges << 24
+__global__ void __launch_bounds__(256) pk_cell_keys_kernel(const u8* mem, u32 sh, u32 shift, u64* keys, u32 env0, u32 env1) {
+    const u32 e = env0 + blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= env1) return;
+    const u32 w = PK_P_WRAM - 0xC000u;
+    const u64 map = mem[pk_img_off(e, w + 0xD35Eu, sh)], x = mem[pk_img_off(e, w + 0xD362u, sh)];
+    const u64 y = mem[pk_img_off(e, w + 0xD361u, sh)], badges = mem[pk_img_off(e, w + 0xD356u, sh)];
+    keys[e] = map | (x >> shift) << 8 | (y >> shift) << 16 | badges << 24;
+}
+
+static inline dim3 pk_arch_grid(const PkArchArgs& a) { return dim3((a.env1 - a.env0 + 255u) / 256u); }
+
+// phases 1-4 of pk_archive_update; the per-call words are cleared
+hipError_t pk_launch_arch_update(const PkArchArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(pk_arch_claim_kernel, pk_arch_grid(a), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(pk_arch_best_kernel, pk_arch_grid(a), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(PK_K1_KERNEL_ARCH_RANK, dim3(1), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(pk_arch_commit_kernel, pk_arch_grid(a), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t pk_launch_arch_draw(const PkArchArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(PK_K1_KERNEL_ARCH_SCAN, dim3(1), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(pk_arch_draw_kernel, pk_arch_grid(a), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t pk_launch_arch_out(const PkArchArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(pk_arch_out_kernel, pk_arch_grid(a), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t pk_launch_cell_keys(const u8* mem, u32 sh, u32 shift, u64* keys, u32 env0, u32 env1, hipStream_t s) {
+    hipLaunchKernelGGL(pk_cell_keys_kernel, dim3((env1 - env0 + 255u) / 256u), dim3(256), 0, s, mem, sh, shift, keys, env0, env1);
     return hipGetLastError();
 }

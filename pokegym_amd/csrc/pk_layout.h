@@ -210,3 +210,49 @@ struct PkBankArgs {
     uint32_t env0, env1;
     uint32_t ilv_sh;
 };
+
+// Exploration archive on the bank (pk_archive_*): cell c owns bank slot slot0 + c and keeps the best
+// episode seen under its key.  Persistent part: the header words, the per-cell records and an
+// open-addressing index key -> cell of i_mask + 1 >= 2 * n_cells entries (accepted cells only).
+// Per-call part (pk_archive_update): a scratch table of s_mask + 1 >= 2 * count entries for the
+// keys the index does not hold, the per-cell and per-entry winner words, and per-env words.
+#define PK_ARCH_MAX_CELLS 65536u
+#define PK_ARCH_NOKEY 0xFFFFFFFFFFFFFFFFull   // the reserved key: "no cell", and an empty table entry
+#define PK_ARCH_NONE 0xFFFFFFFFu
+#define PK_ARCH_PRE 8u                        // wave pre-reduction rounds before lanes go to memory alone
+enum { PK_AH_USED = 0, PK_AH_OVERFLOW, PK_AH_DRAWS, PK_AH_CUR, PK_AH_TOTAL, PK_AH_WORDS = 8 };
+
+struct PkArchArgs {
+    uint64_t* hdr;               // [PK_AH_WORDS]: cells in use, overflow, draw calls, the running
+                                 // explore's call number and total weight
+    uint64_t* a_key;             // [n_cells]
+    double* a_score;             // [n_cells] the record's score ...
+    uint32_t* a_len;             // ... and length (the winner's PK_R_TIME)
+    uint32_t* a_visits;
+    uint32_t* a_picks;
+    uint64_t* prefix;            // [n_cells] inclusive prefix sums of the weights (explore)
+    uint64_t* i_key;             // index: key (PK_ARCH_NOKEY = empty) ...
+    uint32_t* i_cell;            // ... and its cell
+    uint64_t* c_max;             // per call, per cell: best candidate score (encoded), 0 = none ...
+    uint64_t* c_le;              // ... and the least length << 32 | env among those with that score
+    uint64_t* s_key;             // scratch entries: key, the same two winner words,
+    uint64_t* s_max;
+    uint64_t* s_le;
+    uint32_t* s_first;           // the lowest env that reached the key, the envs that did,
+    uint32_t* s_cnt;
+    uint32_t* s_cell;            // and the cell the key was given (PK_ARCH_NONE: the archive was full)
+    uint32_t* tgt;               // [npad] per env: its cell, n_cells + its scratch entry, or PK_ARCH_NONE
+    uint8_t* flag;               // [npad] the env is the first of a new key
+    int32_t* map;                // [npad] the slot map handed to the bank kernels
+    const uint64_t* keys;        // caller's arrays
+    const double* scores;
+    const uint8_t* mask;
+    const uint32_t* time_reg;    // regs + PK_R_TIME * npad
+    uint32_t* b_rejects;
+    const int32_t* src;          // the bank's validated slot per env (PkBankArgs.src)
+    int32_t* out;                // caller's slot_of_env_out
+    uint64_t seed;
+    uint32_t i_mask, s_mask;
+    uint32_t n_cells, slot0;
+    uint32_t env0, env1;
+};

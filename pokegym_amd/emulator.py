@@ -236,6 +236,69 @@ class BatchedEmulator:
         check(self._L.pk_bank_rejects(self._h, ctypes.byref(v)), "pk_bank_rejects")
         return int(v.value)
 
+    # -- exploration archive on the bank (stream-ordered except create / read) ------------
+    def archive_create(self, slot0: int, n_cells: int, seed: int = 0):
+        """An archive of n_cells cells over bank slots [slot0, slot0 + n_cells) (pk_archive_create;
+        once, synchronous; needs bank_enable_episodes)."""
+        check(self._L.pk_archive_create(self._h, int(slot0), int(n_cells), int(seed) & (2 ** 64 - 1)), "pk_archive_create")
+
+    @property
+    def archive_cells(self) -> int:
+        return int(self._L.pk_archive_cells(self._h))
+
+    def _full(self, t: torch.Tensor | None, dtype, what: str):
+        """Pointer of a full-size per-env argument (None stays NULL)."""
+        if t is None:
+            return None
+        if t.dtype != dtype or t.device != self.device or t.numel() != self.n or not t.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous {dtype} tensor of n_envs elements on the emulator's device")
+        return ctypes.c_void_p(t.data_ptr())
+
+    def cell_keys(self, shift: int = 0, out: torch.Tensor | None = None, env0: int = 0, count: int | None = None):
+        """int64 (n,) cell keys map | (x >> shift) << 8 | (y >> shift) << 16 | badges << 24 of the
+        envs of the range (pk_cell_keys, on the current stream); the rest of `out` is untouched."""
+        if out is None:
+            out = torch.zeros(self.n, dtype=torch.int64, device=self.device)
+        count = self.n - env0 if count is None else count
+        check(self._L.pk_cell_keys(self._h, int(shift), self._full(out, torch.int64, "keys"), env0, count,
+                                   self._stream()), "pk_cell_keys")
+        return out
+
+    def archive_update(self, keys: torch.Tensor, scores: torch.Tensor, mask: torch.Tensor | None = None,
+                       env0: int = 0, count: int | None = None, out: torch.Tensor | None = None):
+        """Enter the envs of the range into the archive under keys (int64: the 64 key bits; -1 is the
+        reserved "no cell") with scores (float64; NaN takes no part), full-size tensors; every
+        cell's new best env is checkpointed into the cell's slot (pk_archive_update, on the
+        current stream).  out (int32, full size) receives the winners' slots over the range, -1 else."""
+        count = self.n - env0 if count is None else count
+        check(self._L.pk_archive_update(self._h, self._full(keys, torch.int64, "keys"),
+                                        self._full(scores, torch.float64, "scores"), self._full(mask, torch.uint8, "mask"),
+                                        env0, count, self._full(out, torch.int32, "out"), self._stream()),
+              "pk_archive_update")
+        return out
+
+    def archive_explore(self, mask: torch.Tensor | None = None, env0: int = 0, count: int | None = None,
+                        out: torch.Tensor | None = None):
+        """Every masked env of the range draws a cell by visit count and resumes the episode in its
+        slot (pk_archive_explore, on the current stream).  out receives the slots drawn, -1 else."""
+        count = self.n - env0 if count is None else count
+        check(self._L.pk_archive_explore(self._h, self._full(mask, torch.uint8, "mask"), env0, count,
+                                         self._full(out, torch.int32, "out"), self._stream()), "pk_archive_explore")
+        return out
+
+    def archive_read(self) -> dict:
+        """The archive as host arrays (pk_archive_read; synchronous): used, overflow, and per cell
+        keys (uint64), scores, lengths, visits, picks."""
+        k = self.archive_cells
+        used, overflow = ctypes.c_uint32(), ctypes.c_uint64()
+        keys, scores = np.zeros(k, np.uint64), np.zeros(k, np.float64)
+        lengths, visits, picks = np.zeros(k, np.uint32), np.zeros(k, np.uint32), np.zeros(k, np.uint32)
+        check(self._L.pk_archive_read(self._h, ctypes.byref(used), *(ctypes.c_void_p(a.ctypes.data) for a in
+                                                                    (keys, scores, lengths, visits, picks)),
+                                      ctypes.byref(overflow)), "pk_archive_read")
+        return {"used": int(used.value), "overflow": int(overflow.value), "keys": keys, "scores": scores,
+                "lengths": lengths, "visits": visits, "picks": picks}
+
     def set_episode_params(self, max_episode_steps: int, reward_scale: float):
         """Episode length and reward scale of the following steps (Environment.reset's arguments,
         environment.py:1233, :1258-1259); call before the reset they belong to."""

@@ -245,7 +245,7 @@ class VecEnv:
                  reload_on_reset: bool = False, env_offset: int = 0, log_interval: int = 128, emulator=None,
                  heatmap: bool = False, reward: bool = True, power_on: bool = False, batch_size: int | None = None,
                  state_pool=None, pool_seed: int = 0, bank_slots: int = 0, bank_episodes: bool = False,
-                 fork_slots: int = 0):
+                 fork_slots: int = 0, archive_cells: int = 0, archive_seed: int = 0, archive_shift: int = 0):
         """reward=False: the screen-obs env of configs[3] — obs is the (144, 160) u8 screen, rewards are
         0 and episodes end at max_episode_steps.  power_on=True starts (and resets) every env from
         the cartridge's power-on state instead of a savestate.
@@ -263,7 +263,14 @@ class VecEnv:
         reward bookkeeping, so a resumed env continues exactly as the saved one would have, and
         this class's per-env episode return / length and start slot travel with it.  fork_slots
         reserves that many scratch slots after the pool's and the user's for fork(): the number of
-        distinct source envs one fork() call can copy."""
+        distinct source envs one fork() call can copy.
+
+        archive_cells=K (needs bank_episodes=True) adds K more slots after those and an exploration
+        archive over them (pk_archive_*): archive_update() keeps the best episode per cell key,
+        archive_explore(mask) resumes envs from cells drawn by visit count with archive_seed;
+        archive_shift is cell_keys()'s coordinate shift.  Both are calls of the training loop between
+        steps: the auto-reset path does not explore, and the archive is not driven per sub-batch
+        on the sub-batch streams."""
         self.batch_size = batch_size or num_envs
         if num_envs % self.batch_size:
             raise ValueError("batch_size must divide num_envs")
@@ -332,12 +339,18 @@ class VecEnv:
             raise ValueError("bank_episodes=True needs the reward stack (reward=True)")
         if self.fork_slots and not bank_episodes:
             raise ValueError("fork_slots needs bank_episodes=True")
-        if state_pool is not None or bank_slots or self.fork_slots:
+        self.archive_cells, self.archive_shift = int(archive_cells), int(archive_shift)
+        self._arch0 = 0             # first slot of the archive's cells
+        self._arch_out = None
+        if self.archive_cells and not bank_episodes:
+            raise ValueError("archive_cells needs bank_episodes=True")
+        if state_pool is not None or bank_slots or self.fork_slots or self.archive_cells:
             pool = [st if isinstance(st, (bytes, bytearray)) else _read(st) for st in (state_pool or [])]
             if state_pool is not None and not pool:
                 raise ValueError("state_pool is empty")
             self._fork0 = len(pool) + int(bank_slots)
-            self.emu.bank_create(self._fork0 + self.fork_slots)
+            self._arch0 = self._fork0 + self.fork_slots
+            self.emu.bank_create(self._arch0 + self.archive_cells)
             for k, st in enumerate(pool):
                 self.emu.bank_put(k, st)
             self.pool_size = len(pool)
@@ -352,11 +365,14 @@ class VecEnv:
                 self.emu.bank_enable_episodes()
                 # (one entry past the last slot takes the writes of out-of-range slots, which the
                 # device rejects; _ck_valid mirrors the device's "holds an episode" flag)
-                k = self._fork0 + self.fork_slots + 1
+                k = self._arch0 + self.archive_cells + 1
                 self._ck_return = torch.zeros(k, dtype=torch.float64, device=self.device)
                 self._ck_length = torch.zeros(k, dtype=torch.float64, device=self.device)
                 self._ck_slots = torch.full((k,), -1, dtype=torch.int32, device=self.device)
                 self._ck_valid = torch.zeros(k, dtype=torch.bool, device=self.device)
+                if self.archive_cells:
+                    self.emu.archive_create(self._arch0, self.archive_cells, archive_seed)
+                    self._arch_out = torch.full((n_phys,), -1, dtype=torch.int32, device=self.device)
         elif bank_episodes:
             raise ValueError("bank_episodes=True needs a bank: state_pool, bank_slots or fork_slots")
 
@@ -489,6 +505,77 @@ class VecEnv:
         slot_of = {e: self._fork0 + k for k, e in enumerate(uniq)}
         self.checkpoint_to_bank(uniq, [slot_of[e] for e in uniq], check=False)
         self.resume_from_bank(dst, [slot_of[e] for e in src])
+
+    def _physical(self, values: torch.Tensor, fill, dtype) -> torch.Tensor:
+        """A per-env tensor (env order) as a full-size emulator-order one, padding envs = fill."""
+        values = torch.as_tensor(values, device=self.device).reshape(-1).to(dtype)
+        if values.numel() != self.num_envs:
+            raise ValueError("a per-env argument must have num_envs elements")
+        if not self._padded:
+            return values.contiguous()
+        out = torch.full((self.emu.n,), fill, dtype=dtype, device=self.device)
+        out[self._phys] = values
+        return out
+
+    def cell_keys(self) -> torch.Tensor:
+        """The cell key of every env (int64, env order): pk_cell_keys with archive_shift."""
+        return self._logical(self.emu.cell_keys(self.archive_shift))
+
+    def archive_update(self, scores=None, keys=None, mask=None) -> torch.Tensor:
+        """Enter every env (those with mask[e] != 0) into the archive: scores default to the running
+        episode return (stats.ep_return), keys to cell_keys(); per-env tensors in env order.  Each
+        cell's new best episode is checkpointed into the cell's slot together with this class's
+        episode return / length and start slot.  On the current stream after a pipeline join, like
+        checkpoint_to_bank; no host sync.  Returns the slot each env won (int32, env order, -1 else)."""
+        if self._arch_out is None:
+            raise RuntimeError("VecEnv(archive_cells=...) keeps the archive")
+        self._join_streams()
+        scores = self._physical(self.stats.ep_return if scores is None else scores, float("nan"), torch.float64)
+        keys = self.emu.cell_keys(self.archive_shift) if keys is None else self._physical(keys, -1, torch.int64)
+        # padding envs never take part: their mask byte is 0
+        mask = self._physical(torch.ones(self.num_envs, dtype=torch.uint8, device=self.device) if mask is None
+                              else torch.as_tensor(mask, device=self.device) != 0, 0, torch.uint8)
+        self.emu.archive_update(keys, scores, mask, out=self._arch_out)
+        won = self._logical(self._arch_out).long()
+        last = self._ck_return.numel() - 1
+        slots = torch.where(won >= 0, won, last)
+        self._ck_return[slots] = self.stats.ep_return
+        self._ck_length[slots] = self.stats.ep_length
+        self._ck_valid[slots] = True
+        self._ck_valid[last] = False
+        if self._slots is not None:
+            self._ck_slots[slots] = self._logical(self._slots)
+        return won.to(torch.int32)
+
+    def archive_explore(self, mask) -> torch.Tensor:
+        """Every env with mask[e] != 0 draws a cell (weight 1 / sqrt(visits + picks + 1)) and continues
+        the episode kept there, as resume_from_bank does it; no host sync.  Returns the slot each
+        env resumed from (int32, env order, -1 for the others and for rejects)."""
+        if self._arch_out is None:
+            raise RuntimeError("VecEnv(archive_cells=...) keeps the archive")
+        self._join_streams()
+        mask = self._physical(torch.as_tensor(mask, device=self.device) != 0, 0, torch.uint8)
+        self.emu.archive_explore(mask, out=self._arch_out)
+        drawn = self._logical(self._arch_out).long()
+        last = self._ck_return.numel() - 1
+        slots = torch.where(drawn >= 0, drawn, last)
+        ok = (drawn >= 0) & self._ck_valid[slots]
+        self.stats.ep_return.copy_(torch.where(ok, self._ck_return[slots], self.stats.ep_return))
+        self.stats.ep_length.copy_(torch.where(ok, self._ck_length[slots], self.stats.ep_length))
+        if self._slots is not None:
+            cur = self._logical(self._slots)
+            new = torch.where(ok, self._ck_slots[slots], cur)
+            if self._padded:
+                self._slots[self._phys] = new
+            else:
+                self._slots.copy_(new)
+        return drawn.to(torch.int32)
+
+    def archive_state(self) -> dict:
+        """The archive as host arrays (emu.archive_read; synchronous)."""
+        if self._arch_out is None:
+            raise RuntimeError("VecEnv(archive_cells=...) keeps the archive")
+        return self.emu.archive_read()
 
     def _range(self, b: int) -> slice:
         return slice(b * self.batch_size, (b + 1) * self.batch_size)
