@@ -33,6 +33,8 @@
  *                    and the Environment's per-episode attributes) saved to and continued from a slot
  *   pk_archive_update / pk_archive_explore   no reference equivalent: the best episode per cell key,
  *                    kept in bank slots, and envs resumed from cells drawn by visit count
+ *   pk_traj_enable / pk_traj_get / pk_bank_traj_get   no reference equivalent: the actions of every
+ *                    episode, recorded per env and carried through checkpoints, resumes and the archive
  * With PK_F_REWARD, pk_step also runs the reward stack of Environment.step
  * (environment.py:1338-1612) and pk_reset follows Environment.reset (:1233-1334).
  */
@@ -45,7 +47,7 @@
 extern "C" {
 #endif
 
-#define PK_ABI_VERSION 9
+#define PK_ABI_VERSION 10
 #define PK_STATE_V9_BYTES 142610u
 #define PK_SCREEN_ROWS 144u
 #define PK_SCREEN_COLS 160u
@@ -330,6 +332,65 @@ int pk_archive_explore(pk_handle* h, const uint8_t* mask_dev, uint32_t env0, uin
                        int32_t* slot_of_env_out_dev, void* stream);
 int pk_archive_read(pk_handle* h, uint32_t* used, uint64_t* keys, double* scores, uint32_t* lengths,
                     uint32_t* visits, uint32_t* picks, uint64_t* overflow);
+
+/* Action trajectories: how an env got where it is.  After pk_traj_enable every env has
+ *   actions  u8[capacity]  the action of every step since the env's last reset, one byte per step
+ *   origin   i32           the bank slot the episode's machine was reloaded from, -1 = the handle's
+ *                          template
+ *   flags    u8            PK_TRAJ_* bits
+ * and a length, the env's step counter clamped to the capacity.  Emulator and reward stack are
+ * deterministic, so resetting an env from `origin` and stepping it through `actions` rebuilds the
+ * machine, the rewards and the whole episode bookkeeping bit for bit — while flags is 0:
+ *   PK_TRAJ_BROKEN    the actions no longer determine the state: the env's machine was changed
+ *                     from outside (pk_bank_load, pk_load_env, pk_poke: the envs touched; pk_set_ram:
+ *                     every env), its last reset did not reload the machine (with PK_F_REWARD and
+ *                     without PK_F_RELOAD_ON_RESET only an env's first reset reloads; origin is -1
+ *                     then), the env had already stepped when pk_traj_enable was called, or the
+ *                     rows were reallocated.  Recording goes on; a reloading reset clears the flag.
+ *   PK_TRAJ_OVERFLOW  the env was stepped past the capacity — only possible by stepping a done env
+ *                     without resetting it; the first `capacity` actions are intact.
+ *   PK_TRAJ_EMPTY     pk_bank_traj_get only: the slot holds no episode.
+ * An origin names a slot's CONTENT at the time of the reset: the caller keeps the slots it resets
+ * from unchanged for as long as it wants to replay (VecEnv's state-pool slots never change).
+ *
+ * capacity = 3 << (cap_log2 - 2) bytes, cap_log2 the log2 of the seen set's capacity (above): 768
+ * at the 1,024-entry minimum, 24,576 at the default 20,480 steps; always a multiple of 16 and
+ * >= max_episode_steps.  It grows exactly when pk_set_episode_params grows the seen set (on a
+ * handle without PK_F_REWARD: when the same rule would): the rows are reallocated and every env is
+ * flagged PK_TRAJ_BROKEN until its next reloading reset.
+ *
+ * pk_traj_enable (synchronous): once per handle, with or without PK_F_REWARD, before or after
+ * pk_bank_enable_episodes.  On failure (second call, out of memory) the handle is unchanged.
+ * pk_traj_capacity: the capacity, 0 without trajectories.  A handle that never enables them makes
+ * exactly the launches and allocations it made before, and pk_traj_get / pk_bank_traj_get fail on
+ * it with a negative code.  With them, pk_step_range makes one more small launch after the step
+ * kernel, every reset one, and pk_bank_load / pk_set_ram / pk_load_env / pk_poke one.
+ *
+ * Slots: while the bank carries episode parts, every slot carries a trajectory part as well (one
+ * more u8[capacity] row, origin and flags per slot; its length is the step counter of the slot's
+ * episode part).  pk_bank_checkpoint moves env -> slot and pk_bank_resume slot -> env, right after
+ * the episode part and over the same validated list: rejected envs are untouched, many envs may
+ * resume from one slot, a resumed env's later actions are appended to the slot's.  pk_bank_put
+ * and pk_bank_save leave it empty together with the episode part.  pk_archive_update and
+ * pk_archive_explore checkpoint and resume through the same path: a cell's slot holds the
+ * actions that reach the cell, an env that explores from it carries them on.
+ *
+ * pk_traj_get (stream-ordered gather): origin_dev i32[n], len_dev u32[n], flags_dev u8[n],
+ * actions_dev u8[n][capacity] (16-byte aligned), full size and indexed by env; any pointer may be
+ * NULL; the range follows pk_step_range's rule and only its elements are written.
+ * pk_bank_traj_get: the same for slots [slot0, slot0 + count), the arrays indexed by slot - slot0
+ * (actions_dev u8[count][capacity]); a slot without an episode part reads as origin -1, length
+ * 0, flags PK_TRAJ_EMPTY.  In both, the bytes of a row from the length on are written as 0xFF, so
+ * two results compare byte for byte. */
+#define PK_TRAJ_BROKEN 1u
+#define PK_TRAJ_OVERFLOW 2u
+#define PK_TRAJ_EMPTY 4u
+int pk_traj_enable(pk_handle* h);
+uint32_t pk_traj_capacity(const pk_handle* h);
+int pk_traj_get(pk_handle* h, uint32_t env0, uint32_t count, int32_t* origin_dev, uint32_t* len_dev,
+                uint8_t* flags_dev, uint8_t* actions_dev, void* stream);
+int pk_bank_traj_get(pk_handle* h, uint32_t slot0, uint32_t count, int32_t* origin_dev, uint32_t* len_dev,
+                     uint8_t* flags_dev, uint8_t* actions_dev, void* stream);
 
 /* Emulated instructions executed by the last pk_step, summed over envs (synchronous). */
 int pk_last_instr_count(pk_handle* h, uint64_t* out);

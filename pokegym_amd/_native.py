@@ -12,11 +12,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # PK_LIB selects an alternative in-tree build (A/B kernel experiments); default: lib/libpokegym_amd.so
 LIB_PATH = os.environ.get("PK_LIB") or os.path.join(HERE, "lib", "libpokegym_amd.so")
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 PK_F_RENDER = 1
 PK_F_REWARD = 2
 PK_F_RELOAD_ON_RESET = 4
 PK_F_HEATMAP = 8
+PK_TRAJ_BROKEN = 1
+PK_TRAJ_OVERFLOW = 2
+PK_TRAJ_EMPTY = 4
 HEAT_SHAPE = (444, 436)
 OBS_SHAPE = (72, 80, 4)
 # PK_ERR_* -> the exception the reference raises at that point (include/pokegym_amd.h)
@@ -36,7 +39,8 @@ EXPORTS = ("pk_create", "pk_destroy", "pk_last_error", "pk_abi_version", "pk_res
            "pk_reset_from", "pk_bank_rejects",
            "pk_bank_enable_episodes", "pk_bank_has_episodes", "pk_bank_checkpoint", "pk_bank_resume",
            "pk_archive_create", "pk_archive_cells", "pk_cell_keys", "pk_archive_update", "pk_archive_explore",
-           "pk_archive_read")
+           "pk_archive_read",
+           "pk_traj_enable", "pk_traj_capacity", "pk_traj_get", "pk_bank_traj_get")
 
 
 class PkConfig(ctypes.Structure):
@@ -106,6 +110,7 @@ def bind(L):
     bind_v7(L)
     bind_v8(L)
     bind_v9(L)
+    bind_v10(L)
 
 
 def bind_v2(L):
@@ -170,6 +175,17 @@ def bind_v9(L):
     L.pk_archive_update.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp]
     L.pk_archive_explore.argtypes = [vp, vp, u32, u32, vp, vp]
     L.pk_archive_read.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+
+
+def bind_v10(L):
+    """argtypes of the action trajectories (ABI v10; shared with the host-simulation test build)."""
+    vp = ctypes.c_void_p
+    u32 = ctypes.c_uint32
+    L.pk_traj_enable.argtypes = [vp]
+    L.pk_traj_capacity.argtypes = [vp]
+    L.pk_traj_capacity.restype = u32
+    L.pk_traj_get.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp]
+    L.pk_bank_traj_get.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp]
 
 
 def check(rc: int, what: str):

@@ -47,6 +47,11 @@ hipError_t pk_launch_arch_draw(const PkArchArgs& a, hipStream_t s);
 hipError_t pk_launch_arch_out(const PkArchArgs& a, hipStream_t s);
 hipError_t pk_launch_cell_keys(const uint8_t* mem, uint32_t sh, uint32_t shift, uint64_t* keys, uint32_t env0,
                                uint32_t env1, hipStream_t s);
+hipError_t pk_launch_traj_record(const PkTrajArgs& a, hipStream_t s);
+hipError_t pk_launch_traj_reset(const PkTrajArgs& a, hipStream_t s);
+hipError_t pk_launch_traj_mark(const PkTrajArgs& a, hipStream_t s);
+hipError_t pk_launch_traj_move(const PkTrajArgs& a, hipStream_t s);
+hipError_t pk_launch_traj_get(const PkTrajArgs& a, hipStream_t s);
 
 namespace {
 
@@ -304,6 +309,15 @@ struct pk_handle {
     uint8_t* a_fix = nullptr;
     uint8_t* a_ones = nullptr;
     uint8_t* a_zero = nullptr;
+    // action trajectories (pk_traj_enable; pk_reward.h PkTrajArgs), traj_cap = 0 without them: the
+    // envs' rows, origins and flags, and the slots' while the bank carries episode parts
+    uint32_t traj_cap = 0;
+    uint8_t* t_act = nullptr;
+    int32_t* t_origin = nullptr;
+    uint32_t* t_flags = nullptr;
+    uint8_t* bt_act = nullptr;
+    int32_t* bt_origin = nullptr;
+    uint32_t* bt_flags = nullptr;
     // profiling: 4 events per profiled step (start, after K1, after K2, after K4+K3)
     bool prof = false;
     std::vector<hipEvent_t> ev_pool;
@@ -344,7 +358,8 @@ void pk_destroy(pk_handle* h) {
                     h->t_lat, h->t_screen, h->scratch, h->rs, h->rsd, h->seen, h->mask, h->cutc, h->obs, h->reload,
                     h->lists, h->dbg, h->info, h->info_flag, h->heat, h->info_bits, h->bank_slot_s, h->slot_bank_s,
                     h->b_mem, h->b_regs, h->b_lat, h->b_screen, h->b_filled, h->b_rejects, h->b_lists, h->b_src,
-                    h->e_fields, h->e_seen, h->e_mask, h->e_cutc, h->b_ep_filled, h->a_fix, h->a_ones, h->a_zero};
+                    h->e_fields, h->e_seen, h->e_mask, h->e_cutc, h->b_ep_filled, h->a_fix, h->a_ones, h->a_zero,
+                    h->t_act, h->t_origin, h->t_flags, h->bt_act, h->bt_origin, h->bt_flags};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     delete h;
@@ -596,11 +611,103 @@ static int check_range(pk_handle* h, uint32_t env0, uint32_t count) {
     return 0;
 }
 
+// ---- action trajectories: the pieces the other calls use (the entry points are at the end) ------
+
+static PkTrajArgs traj_args(pk_handle* h, uint32_t env0, uint32_t env1) {
+    PkTrajArgs a;
+    memset(&a, 0, sizeof a);
+    a.time_reg = h->regs + (size_t)PK_R_TIME * h->npad;
+    a.act = h->t_act; a.origin = h->t_origin; a.flags = h->t_flags;
+    a.b_act = h->bt_act; a.b_origin = h->bt_origin; a.b_flags = h->bt_flags;
+    a.e_fields = h->e_fields; a.b_ep_filled = h->b_ep_filled;
+    a.cap = h->traj_cap; a.env0 = env0; a.env1 = env1;
+    return a;
+}
+
+// the reset of [env0, env1) just made: the masked envs start an empty list at the slot src names
+// (null: the template); with a reload array, those it leaves out kept their machine (PK_TRAJ_BROKEN)
+static int traj_reset(pk_handle* h, const uint8_t* mask, const uint8_t* reload, const int32_t* src, uint32_t env0,
+                      uint32_t env1, hipStream_t s) {
+    if (!h->traj_cap) return 0;
+    PkTrajArgs a = traj_args(h, env0, env1);
+    a.mask = mask; a.reload = reload; a.src = src;
+    HIPCHK(pk_launch_traj_reset(a, s));
+    return 0;
+}
+
+// PK_TRAJ_BROKEN for the envs of a device-built list (cnt, ids; at most env1 - env0), or without
+// one for every env of [env0, env1)
+static int traj_mark(pk_handle* h, const uint32_t* cnt, const uint32_t* ids, uint32_t env0, uint32_t env1, hipStream_t s) {
+    if (!h->traj_cap) return 0;
+    PkTrajArgs a = traj_args(h, env0, env1);
+    a.cnt = cnt; a.ids = ids; a.items = env1 - env0;
+    HIPCHK(pk_launch_traj_mark(a, s));
+    return 0;
+}
+
+// one set of trajectory parts: rows of cap bytes with an origin and a flag word each
+struct TrajBufs {
+    uint8_t* act = nullptr;
+    int32_t* origin = nullptr;
+    uint32_t* flags = nullptr;
+};
+
+static void traj_free(TrajBufs& b) {
+    void* ptrs[] = {b.act, b.origin, b.flags};
+    for (void* p : ptrs)
+        if (p) (void)hipFree(p);
+    b = TrajBufs();
+}
+
+// rows zeroed, origins -1, flags as given (one word per row); all or nothing
+static int traj_alloc(size_t rows, uint32_t cap, const std::vector<uint32_t>& flags, TrajBufs& b) {
+    hipError_t e = hipMalloc((void**)&b.act, rows * cap);
+    if (e == hipSuccess) e = hipMalloc((void**)&b.origin, rows * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&b.flags, rows * 4);
+    if (e == hipSuccess) e = hipMemset(b.act, 0, rows * cap);
+    if (e == hipSuccess) e = hipMemset(b.origin, 0xFF, rows * 4);
+    if (e == hipSuccess) e = hipMemcpy(b.flags, flags.data(), rows * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) return 0;
+    traj_free(b);
+    (void)hipGetLastError();
+    return fail(-ENOMEM, "trajectories of %zu rows of %u bytes: %s", rows, cap, hipGetErrorString(e));
+}
+
+static uint32_t traj_cap_of(uint32_t cap_log2) { return 3u << (cap_log2 - 2u); }
+
+// the trajectory parts of a seen set grown to 1 << need: new rows for the envs, every one flagged
+// PK_TRAJ_BROKEN (its actions stay behind), and for the slots where the bank has them
+static int traj_grow_alloc(pk_handle* h, uint32_t need, TrajBufs& envs, TrajBufs& slots) {
+    if (!h->traj_cap) return 0;
+    int rc = traj_alloc(h->npad, traj_cap_of(need), std::vector<uint32_t>(h->npad, PK_TRAJ_BROKEN), envs);
+    if (!rc && h->bt_act && (rc = traj_alloc(h->bank_n, traj_cap_of(need), std::vector<uint32_t>(h->bank_n, 0u), slots)))
+        traj_free(envs);
+    return rc;
+}
+
+static void traj_grow_commit(pk_handle* h, uint32_t need, TrajBufs& envs, TrajBufs& slots) {
+    if (!h->traj_cap) return;
+    TrajBufs old_e, old_s;
+    old_e.act = h->t_act; old_e.origin = h->t_origin; old_e.flags = h->t_flags;
+    old_s.act = h->bt_act; old_s.origin = h->bt_origin; old_s.flags = h->bt_flags;
+    traj_free(old_e);
+    h->t_act = envs.act; h->t_origin = envs.origin; h->t_flags = envs.flags;
+    if (slots.act) {
+        traj_free(old_s);
+        h->bt_act = slots.act; h->bt_origin = slots.origin; h->bt_flags = slots.flags;
+    }
+    h->traj_cap = traj_cap_of(need);
+}
+
 int pk_reset_range(pk_handle* h, uint32_t env0, uint32_t count, const uint8_t* mask, void* stream) {
     int rc;
     if ((rc = check_range(h, env0, count))) return rc;
     const uint32_t env1 = env0 + count;
-    if (!(h->flags & PK_F_REWARD)) return template_reset(h, mask, env0, env1, stream);
+    if (!(h->flags & PK_F_REWARD)) {
+        if ((rc = template_reset(h, mask, env0, env1, stream))) return rc;
+        return traj_reset(h, mask, nullptr, nullptr, env0, env1, (hipStream_t)stream);
+    }
     HIPCHK(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
     PkRewardArgs r = reward_args(h, env0, env1);
@@ -608,6 +715,7 @@ int pk_reset_range(pk_handle* h, uint32_t env0, uint32_t count, const uint8_t* m
     HIPCHK(pk_launch_rreset_pre(r, s));
     if ((rc = template_reset(h, h->reload, env0, env1, stream))) return rc;
     HIPCHK(pk_launch_rreset_post(r, s));
+    if ((rc = traj_reset(h, mask, h->reload, nullptr, env0, env1, s))) return rc;
     // the observation of the reset envs only (list of the masked envs)
     HIPCHK(hipMemsetAsync(list_cnt(h, env0, 1), 0, 4, s));
     HIPCHK(pk_launch_list(mask, env0, env1, list_cnt(h, env0, 1), list_ids(h, env0, 1), s));
@@ -641,7 +749,7 @@ int pk_set_ram(pk_handle* h, uint16_t addr, uint32_t len, const uint8_t* dense, 
     HIPCHK(hipSetDevice(h->device));
     uint32_t phys0 = wram ? PK_P_WRAM + (addr & 0x1FFFu) : PK_P_HRAM + (addr - 0xFF80u);
     HIPCHK(pk_launch_ram_copy(h->mem, const_cast<uint8_t*>(dense), h->n, h->ilv_sh, phys0, len, 0, (hipStream_t)stream));
-    return 0;
+    return traj_mark(h, nullptr, nullptr, 0, h->n, (hipStream_t)stream);
 }
 
 // K1 envs per wave for a launch of `count` envs (measured, profiles/r02_sweep_*, r02_ab/ab_prio.txt):
@@ -740,6 +848,11 @@ int pk_step_range(pk_handle* h, uint32_t env0, uint32_t count, const uint8_t* ac
     PkStepArgs a = step_args(h, actions, env0, env1);
     if (h->prof && (rc = prof_event(h, s))) return rc;
     HIPCHK(a.small ? pk_launch_step_small(a, s) : pk_launch_step(a, s));
+    if (h->traj_cap) {
+        PkTrajArgs t = traj_args(h, env0, env1);
+        t.actions = actions;
+        HIPCHK(pk_launch_traj_record(t, s));
+    }
     if (h->prof && (rc = prof_event(h, s))) return rc;
     if (a.render_last) HIPCHK(pk_launch_render(a, s));
     if (h->prof && (rc = prof_event(h, s))) return rc;
@@ -864,6 +977,8 @@ int pk_load_env(pk_handle* h, uint32_t env, const uint8_t* in, uint64_t len) {
             HIPCHK(hipMemcpy(h->lat + k * h->lat_stride + ((size_t)gid * PK_ROWS + y) * PK_LANES + lane,
                              &t.lat[k * PK_ROWS + y], 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->screen + (size_t)env * PK_SCREEN, t.screen.data(), PK_SCREEN, hipMemcpyHostToDevice));
+    if ((rc = traj_mark(h, nullptr, nullptr, env, env + 1, nullptr))) return rc;
+    if (h->traj_cap) HIPCHK(hipDeviceSynchronize());
     return 0;
 }
 
@@ -950,6 +1065,9 @@ int pk_poke(pk_handle* h, uint32_t env, uint16_t addr, uint32_t len, const uint8
     uint32_t regs[PK_NREGS], lat[3 * PK_ROWS];
     int rc = fetch_env(h, env, mem, regs, lat, screen);
     if (rc) return rc;
+    // flagged first: a poke that fails at a later byte has written the earlier ones
+    if ((rc = traj_mark(h, nullptr, nullptr, env, env + 1, nullptr))) return rc;
+    if (h->traj_cap) HIPCHK(hipDeviceSynchronize());
     for (uint32_t i = 0; i < len; i++) {
         uint32_t a = (uint32_t)addr + i, phys;
         int special;
@@ -998,18 +1116,23 @@ int pk_set_episode_params(pk_handle* h, uint32_t max_episode_steps, double rewar
     if (!h) return fail(-EINVAL, "null handle");
     if (max_episode_steps == 0) return fail(-EINVAL, "max_episode_steps must be > 0");
     HIPCHK(hipSetDevice(h->device));
+    uint32_t need = 10;
+    while ((1ull << need) * 3 < ((uint64_t)max_episode_steps + 2) * 4) need++;
+    // the trajectory rows follow the seen set's capacity: allocated first, committed last
+    TrajBufs tj_envs, tj_slots;
     if (h->flags & PK_F_REWARD) {
-        uint32_t need = 10;
-        while ((1ull << need) * 3 < ((uint64_t)max_episode_steps + 2) * 4) need++;
         if (need > h->cap_log2) {
             HIPCHK(hipDeviceSynchronize());
+            int rc = traj_grow_alloc(h, need, tj_envs, tj_slots);
+            if (rc) return rc;
+            auto drop = [&]() { traj_free(tj_envs); traj_free(tj_slots); };
             uint32_t* seen = nullptr;
             const size_t bytes = (size_t)h->npad * (1ull << need) * 4;
-            if (hipMalloc((void**)&seen, bytes) != hipSuccess) return fail(-ENOMEM, "hipMalloc(%zu) for the seen set", bytes);
-            if (hipMemset(seen, 0, bytes) != hipSuccess) { (void)hipFree(seen); return fail(-EIO, "hipMemset failed"); }
+            if (hipMalloc((void**)&seen, bytes) != hipSuccess) { drop(); return fail(-ENOMEM, "hipMalloc(%zu) for the seen set", bytes); }
+            if (hipMemset(seen, 0, bytes) != hipSuccess) { (void)hipFree(seen); drop(); return fail(-EIO, "hipMemset failed"); }
             hipError_t e = pk_launch_seen_rehash(h->seen, h->cap_log2, seen, need, h->rs, h->n, h->npad, nullptr);
             if (e == hipSuccess) e = hipDeviceSynchronize();
-            if (e != hipSuccess) { (void)hipFree(seen); return fail(-EIO, "seen-set rehash: %s", hipGetErrorString(e)); }
+            if (e != hipSuccess) { (void)hipFree(seen); drop(); return fail(-EIO, "seen-set rehash: %s", hipGetErrorString(e)); }
             if (h->b_ep_filled) {
                 // the slots' seen tables follow the envs' size: reallocated, and every episode part
                 // marked empty (a resume from an older checkpoint is then a reject)
@@ -1022,6 +1145,7 @@ int pk_set_episode_params(pk_handle* h, uint32_t max_episode_steps, double rewar
                 if (e != hipSuccess) {
                     if (eseen) (void)hipFree(eseen);
                     (void)hipFree(seen);
+                    drop();
                     (void)hipGetLastError();
                     return fail(-ENOMEM, "episode parts of %u slots at the larger seen set (%zu bytes): %s", h->bank_n, eb,
                                 hipGetErrorString(e));
@@ -1032,7 +1156,15 @@ int pk_set_episode_params(pk_handle* h, uint32_t max_episode_steps, double rewar
             (void)hipFree(h->seen);
             h->seen = seen;
             h->cap_log2 = need;
+            traj_grow_commit(h, need, tj_envs, tj_slots);
         }
+    } else if (h->traj_cap && need > h->cap_log2) {
+        // no seen set to follow: the rows alone keep cap >= max_episode_steps
+        HIPCHK(hipDeviceSynchronize());
+        int rc = traj_grow_alloc(h, need, tj_envs, tj_slots);
+        if (rc) return rc;
+        h->cap_log2 = need;
+        traj_grow_commit(h, need, tj_envs, tj_slots);
     }
     h->max_steps = max_episode_steps;
     h->reward_scale = reward_scale;
@@ -1211,7 +1343,11 @@ int pk_bank_save(pk_handle* h, const int32_t* slots, uint32_t env0, uint32_t cou
 }
 
 int pk_bank_load(pk_handle* h, const int32_t* slots, uint32_t env0, uint32_t count, void* stream) {
-    return bank_move(h, PK_BANK_LOAD, slots, env0, count, stream);
+    int rc = bank_move(h, PK_BANK_LOAD, slots, env0, count, stream);
+    if (rc) return rc;
+    // the envs that took a slot's machine (the call's own list) no longer follow from their actions
+    return traj_mark(h, h->b_lists + 2u * (env0 / PK_LANES), h->b_lists + 2u * h->ngroups + env0, env0, env0 + count,
+                     (hipStream_t)stream);
 }
 
 // template_reset with a slot per env: the selected envs with a usable slot reload from it (bank
@@ -1242,7 +1378,12 @@ int pk_reset_from(pk_handle* h, uint32_t env0, uint32_t count, const uint8_t* ma
     if ((rc = check_range(h, env0, count))) return rc;
     if (!h->bank_n) return fail(-ENOENT, "the handle has no bank (pk_bank_create)");
     const uint32_t env1 = env0 + count;
-    if (!(h->flags & PK_F_REWARD)) return bank_reset(h, mask, slots, env0, env1, stream);
+    // the trajectory origin is the slot pk_bank_list_kernel validated (b_src: -1 for the template,
+    // a rejected slot included)
+    if (!(h->flags & PK_F_REWARD)) {
+        if ((rc = bank_reset(h, mask, slots, env0, env1, stream))) return rc;
+        return traj_reset(h, mask, nullptr, h->b_src, env0, env1, (hipStream_t)stream);
+    }
     HIPCHK(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
     PkRewardArgs r = reward_args(h, env0, env1);
@@ -1250,6 +1391,7 @@ int pk_reset_from(pk_handle* h, uint32_t env0, uint32_t count, const uint8_t* ma
     HIPCHK(pk_launch_rreset_pre(r, s));
     if ((rc = bank_reset(h, h->reload, slots, env0, env1, stream))) return rc;
     HIPCHK(pk_launch_rreset_post(r, s));
+    if ((rc = traj_reset(h, mask, h->reload, h->b_src, env0, env1, s))) return rc;
     HIPCHK(hipMemsetAsync(list_cnt(h, env0, 1), 0, 4, s));
     HIPCHK(pk_launch_list(mask, env0, env1, list_cnt(h, env0, 1), list_ids(h, env0, 1), s));
     r.ocnt = list_cnt(h, env0, 1);
@@ -1272,6 +1414,10 @@ int pk_bank_enable_episodes(pk_handle* h) {
     const size_t K = h->bank_n, seen = K * (1ull << h->cap_log2) * 4;
     uint32_t *f = nullptr, *sn = nullptr, *mk = nullptr, *cc = nullptr;
     uint8_t* fl = nullptr;
+    // on a handle with trajectories the slots carry a trajectory part from the start
+    TrajBufs tb;
+    int rc;
+    if (h->traj_cap && (rc = traj_alloc(K, h->traj_cap, std::vector<uint32_t>(K, 0u), tb))) return rc;
     hipError_t e = hipMalloc((void**)&f, K * PK_EP_WORDS * 4);
     if (e == hipSuccess) e = hipMalloc((void**)&sn, seen);
     if (e == hipSuccess) e = hipMalloc((void**)&mk, K * PK_MASK_WORDS * 4);
@@ -1287,11 +1433,13 @@ int pk_bank_enable_episodes(pk_handle* h) {
         void* ptrs[] = {f, sn, mk, cc, fl};
         for (void* p : ptrs)
             if (p) (void)hipFree(p);
+        traj_free(tb);
         (void)hipGetLastError();
         return fail(-ENOMEM, "episode parts of %zu slots (%zu bytes each): %s", K,
                     (size_t)(seen / K) + (PK_MASK_WORDS + PK_CUTC_CAP + PK_EP_WORDS) * 4 + 1, hipGetErrorString(e));
     }
     h->e_fields = f; h->e_seen = sn; h->e_mask = mk; h->e_cutc = cc; h->b_ep_filled = fl;
+    h->bt_act = tb.act; h->bt_origin = tb.origin; h->bt_flags = tb.flags;
     return 0;
 }
 
@@ -1318,6 +1466,13 @@ static int episode_move(pk_handle* h, uint32_t mode, const int32_t* slots, uint3
     p.npad = h->npad; p.nregs = PK_NREGS; p.cap_log2 = h->cap_log2; p.save = mode == PK_BANK_SAVE ? 1u : 0u;
     p.items = count;
     HIPCHK(pk_launch_ep_move(p, s));
+    if (h->traj_cap) {
+        // the trajectory part over the same list; a resumed env's step counter is the slot's by now
+        PkTrajArgs t = traj_args(h, env0, env0 + count);
+        t.cnt = a.cnt; t.ids = a.ids; t.src = a.src;
+        t.save = p.save; t.items = count;
+        HIPCHK(pk_launch_traj_move(t, s));
+    }
     if (mode == PK_BANK_LOAD) {
         PkRewardArgs r = reward_args(h, env0, env0 + count);
         r.ocnt = a.cnt;
@@ -1497,6 +1652,70 @@ int pk_archive_read(pk_handle* h, uint32_t* used, uint64_t* keys, double* scores
     if (visits) HIPCHK(hipMemcpy(visits, a.a_visits, K * 4, hipMemcpyDeviceToHost));
     if (picks) HIPCHK(hipMemcpy(picks, a.a_picks, K * 4, hipMemcpyDeviceToHost));
     return 0;
+}
+
+// ---- action trajectories ------------------------------------------------------------------------
+
+uint32_t pk_traj_capacity(const pk_handle* h) { return h ? h->traj_cap : 0; }
+
+int pk_traj_enable(pk_handle* h) {
+    if (!h) return fail(-EINVAL, "null handle");
+    if (h->traj_cap) return fail(-EEXIST, "the handle already records trajectories");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipDeviceSynchronize());
+    uint32_t lg = h->cap_log2;
+    if (!(h->flags & PK_F_REWARD)) {
+        // without a seen set nothing has kept cap_log2 up with pk_set_episode_params
+        lg = 10;
+        while ((1ull << lg) * 3 < ((uint64_t)h->max_steps + 2) * 4) lg++;
+    }
+    const uint32_t cap = traj_cap_of(lg);
+    // an env that has already stepped has lost its first actions
+    std::vector<uint32_t> flags(h->npad, 0u);
+    HIPCHK(hipMemcpy(flags.data(), h->regs + (size_t)PK_R_TIME * h->npad, (size_t)h->npad * 4, hipMemcpyDeviceToHost));
+    for (uint32_t& f : flags) f = f ? PK_TRAJ_BROKEN : 0u;
+    TrajBufs envs, slots;
+    int rc;
+    if ((rc = traj_alloc(h->npad, cap, flags, envs))) return rc;
+    // slots that already hold an episode hold no actions for it
+    if (h->b_ep_filled && (rc = traj_alloc(h->bank_n, cap, std::vector<uint32_t>(h->bank_n, PK_TRAJ_BROKEN), slots))) {
+        traj_free(envs);
+        return rc;
+    }
+    h->t_act = envs.act; h->t_origin = envs.origin; h->t_flags = envs.flags;
+    h->bt_act = slots.act; h->bt_origin = slots.origin; h->bt_flags = slots.flags;
+    h->cap_log2 = lg;
+    h->traj_cap = cap;
+    return 0;
+}
+
+static int traj_get(pk_handle* h, bool slots, uint32_t i0, uint32_t count, int32_t* origin, uint32_t* len, uint8_t* flags,
+                    uint8_t* actions, void* stream) {
+    if ((uintptr_t)actions & 15u) return fail(-EINVAL, "actions_dev must be 16-byte aligned");
+    HIPCHK(hipSetDevice(h->device));
+    PkTrajArgs a = traj_args(h, i0, i0 + count);
+    a.slots = slots ? 1u : 0u;
+    a.o_origin = origin; a.o_len = len; a.o_flags = flags; a.o_act = actions;
+    HIPCHK(pk_launch_traj_get(a, (hipStream_t)stream));
+    return 0;
+}
+
+int pk_traj_get(pk_handle* h, uint32_t env0, uint32_t count, int32_t* origin, uint32_t* len, uint8_t* flags, uint8_t* actions,
+                void* stream) {
+    int rc;
+    if ((rc = check_range(h, env0, count))) return rc;
+    if (!h->traj_cap) return fail(-ENOENT, "the handle records no trajectories (pk_traj_enable)");
+    return traj_get(h, false, env0, count, origin, len, flags, actions, stream);
+}
+
+int pk_bank_traj_get(pk_handle* h, uint32_t slot0, uint32_t count, int32_t* origin, uint32_t* len, uint8_t* flags,
+                     uint8_t* actions, void* stream) {
+    if (!h) return fail(-EINVAL, "null handle");
+    if (!h->traj_cap) return fail(-ENOENT, "the handle records no trajectories (pk_traj_enable)");
+    if (!h->bank_n) return fail(-ENOENT, "the handle has no bank (pk_bank_create)");
+    if (count == 0 || (uint64_t)slot0 + count > h->bank_n)
+        return fail(-EINVAL, "slots [%u, +%u) are not inside the bank's %u", slot0, count, h->bank_n);
+    return traj_get(h, true, slot0, count, origin, len, flags, actions, stream);
 }
 
 }  // extern "C"

@@ -119,6 +119,48 @@ struct PkEpArgs {
     uint32_t items;           // upper bound of listed envs (the range's size): sizes the grid
 };
 
+// Action trajectories (pk_traj_enable): per env the actions of its episode so far, one byte per
+// step, with the bank slot the episode started from (origin, -1 = the handle's template) and
+// PK_TRAJ_* flags; the length is the env's step counter PK_R_TIME clamped to the capacity
+// cap = 3 << (cap_log2 - 2), a multiple of 16 that is >= max_episode_steps.  Rows are env-major,
+// u8[npad][cap], so a row is linear memory and starts 16-byte aligned.  When the bank carries
+// episode parts every slot has the same three parts; a slot's length is the step counter of its
+// episode record (e_fields, PK_EP_REGS + PK_R_TIME).  The flags are kept a word per env and slot:
+// the mover makes no byte access.
+#ifndef PK_TRAJ_BROKEN
+#define PK_TRAJ_BROKEN 1u     // == include/pokegym_amd.h
+#define PK_TRAJ_OVERFLOW 2u
+#define PK_TRAJ_EMPTY 4u
+#endif
+
+struct PkTrajArgs {
+    const uint32_t* time_reg; // regs + PK_R_TIME * npad
+    uint8_t* act;             // [npad][cap]
+    int32_t* origin;          // [npad]
+    uint32_t* flags;          // [npad]
+    uint8_t* b_act;           // [n_slots][cap], null while the bank carries no episodes
+    int32_t* b_origin;        // [n_slots]
+    uint32_t* b_flags;        // [n_slots]
+    const uint32_t* e_fields; // [n_slots][PK_EP_WORDS] the slots' episode records (their lengths)
+    const uint8_t* b_ep_filled;
+    const uint8_t* actions;   // record: the step's actions [n]
+    const uint8_t* mask;      // reset: the envs that were reset (null = all)
+    const uint8_t* reload;    // reset: which of them reloaded their machine (null = all)
+    const int32_t* src;       // reset: the slot an env reloaded, -1 = the template (null = template);
+                              // move: the validated slot of every listed env
+    const uint32_t* cnt;      // move / mark: a device-built env list (count, ids); mark without
+    const uint32_t* ids;      // a list covers [env0, env1)
+    int32_t* o_origin;        // get: the caller's arrays, any may be null
+    uint32_t* o_len;
+    uint8_t* o_flags;
+    uint8_t* o_act;
+    uint32_t cap;
+    uint32_t env0, env1;      // env range; get with slots = 1: the slot range
+    uint32_t save;            // move: 1 = env -> slot, 0 = slot -> env
+    uint32_t slots;           // get: read slots (outputs indexed by slot - env0) instead of envs
+    uint32_t items;           // move / mark: upper bound of listed envs, sizes the grid
+};
+
 struct PkRewardArgs {
     uint8_t* mem;             // lane-interleaved RAM images (pk_layout.h)
     uint32_t* regs;           // K1 lane registers (TIME, special IO regs)

@@ -9,6 +9,9 @@
 //                            reload of pk_kernels.hip (reload only on the first reset, :1241).
 //   K3 pk_obs_kernel         render(): screen[::2, ::2] (3 grey channels) + the 72x80 window of
 //                            the visited mask (get_fixed_window, :233-254) -> u8 (72, 80, 4).
+//   pk_ep_move_kernel        episode parts of bank slots <-> envs (pk_bank_checkpoint / _resume).
+//   pk_traj_*_kernel         action trajectories: record beside the step, follow resets, move with
+//                            the episode parts, gather for the caller (pk_reward.h PkTrajArgs).
 //
 // Parity: bit-exact against oracle/reward.py, itself pinned on the reference's own outputs
 // (tests/golden/reward_replay.npz).  Reads go to the same lane-interleaved RAM images K1 runs
@@ -833,6 +836,144 @@ hipError_t pk_launch_ep_move(const PkEpArgs& a, hipStream_t s) {
     const uint64_t items = (uint64_t)a.items * ((pieces + PK_EP_CHUNK - 1u) / PK_EP_CHUNK);
     const u32 grid = items < 65536u ? (u32)(items ? items : 1u) : 65536u;
     hipLaunchKernelGGL(pk_ep_move_kernel, dim3(grid), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// Action trajectories (pk_reward.h PkTrajArgs).  Small kernels beside the step and the movers; a
+// handle without trajectories launches none of them.
+
+// after K1, thread = env of the stepped range: the step's action at index time - 1 (K1 has counted
+// the step); past the capacity — an env stepped on after its episode's end — nothing is stored
+__global__ void __launch_bounds__(256) pk_traj_record_kernel(PkTrajArgs A) {
+    const u32 e = A.env0 + blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= A.env1) return;
+    const u32 t = A.time_reg[e] - 1u;
+    if (t < A.cap) A.act[(size_t)e * A.cap + t] = A.actions[e];
+    else A.flags[e] |= PK_TRAJ_OVERFLOW;
+}
+
+// after a reset, thread = env of the range: a reset env starts an empty list (its step counter is 0)
+// at the state it reloaded — a slot or the template; one that kept its machine starts nowhere known
+__global__ void __launch_bounds__(256) pk_traj_reset_kernel(PkTrajArgs A) {
+    const u32 e = A.env0 + blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= A.env1 || (A.mask && !A.mask[e])) return;
+    const bool reloaded = !A.reload || A.reload[e];
+    A.origin[e] = reloaded && A.src ? A.src[e] : -1;
+    A.flags[e] = reloaded ? 0u : PK_TRAJ_BROKEN;
+}
+
+// the machine of the listed envs (or of every env of [env0, env1)) was changed from outside
+__global__ void __launch_bounds__(256) pk_traj_mark_kernel(PkTrajArgs A) {
+    const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (A.ids) {
+        if (t < *A.cnt) A.flags[A.ids[t]] |= PK_TRAJ_BROKEN;
+    } else if (A.env0 + t < A.env1) {
+        A.flags[A.env0 + t] |= PK_TRAJ_BROKEN;
+    }
+}
+
+// Trajectory mover (pk_bank_checkpoint / pk_bank_resume, after pk_ep_move_kernel over the same
+// list): a workgroup takes one listed env and moves the ceil(len / 16) 16-byte pieces of its row
+// to or from its validated slot, consecutive lanes moving consecutive pieces; origin and flags
+// go as words.  The length is the env's step counter, which the episode mover has already
+// restored on a resume.  Rows are only read on the slot side of a resume, so many envs may name
+// one slot.
+__global__ void __launch_bounds__(256) pk_traj_move_kernel(PkTrajArgs A) {
+    const u32 total = *A.cnt;
+    for (u32 w = blockIdx.x; w < total; w += gridDim.x) {
+        const u32 env = A.ids[w], s = (u32)A.src[env];
+        const u32 time = A.time_reg[env];
+        const u32 pieces = ((time < A.cap ? time : A.cap) + 15u) / 16u;
+        uint4* er = reinterpret_cast<uint4*>(A.act + (size_t)env * A.cap);
+        uint4* br = reinterpret_cast<uint4*>(A.b_act + (size_t)s * A.cap);
+        for (u32 q = threadIdx.x; q < pieces; q += blockDim.x) {
+            if (A.save) br[q] = er[q];
+            else er[q] = br[q];
+        }
+        if (threadIdx.x == 0u) {
+            if (A.save) {
+                A.b_origin[s] = A.origin[env];
+                A.b_flags[s] = A.flags[env];
+            } else {
+                A.origin[env] = A.b_origin[s];
+                A.flags[env] = A.b_flags[s];
+            }
+        }
+    }
+}
+
+// pk_traj_get / pk_bank_traj_get: a workgroup per env (or slot) of the range gathers its row into the
+// caller's buffers, 16 bytes per lane, bytes from the length on written as 0xFF
+__device__ __forceinline__ u32 traj_keep(u32 v, u32 at, u32 len) {
+    return len >= at + 4u ? v : len <= at ? 0xFFFFFFFFu : v | (0xFFFFFFFFu << (8u * (len - at)));
+}
+
+__global__ void __launch_bounds__(256) pk_traj_get_kernel(PkTrajArgs A) {
+    for (u32 i = A.env0 + blockIdx.x; i < A.env1; i += gridDim.x) {
+        int32_t origin = -1;
+        u32 len = 0, flags = PK_TRAJ_EMPTY;
+        const uint4* row = nullptr;
+        if (!A.slots) {
+            origin = A.origin[i];
+            len = A.time_reg[i];
+            flags = A.flags[i];
+            row = reinterpret_cast<const uint4*>(A.act + (size_t)i * A.cap);
+        } else if (A.b_ep_filled && A.b_ep_filled[i]) {
+            origin = A.b_origin[i];
+            len = A.e_fields[(size_t)i * PK_EP_WORDS + PK_EP_REGS + PK_R_TIME];
+            flags = A.b_flags[i];
+            row = reinterpret_cast<const uint4*>(A.b_act + (size_t)i * A.cap);
+        }
+        len = len < A.cap ? len : A.cap;
+        const u32 o = A.slots ? i - A.env0 : i;
+        if (threadIdx.x == 0u) {
+            if (A.o_origin) A.o_origin[o] = origin;
+            if (A.o_len) A.o_len[o] = len;
+            if (A.o_flags) A.o_flags[o] = (u8)flags;
+        }
+        if (!A.o_act) continue;
+        uint4* out = reinterpret_cast<uint4*>(A.o_act + (size_t)o * A.cap);
+        for (u32 q = threadIdx.x; q < A.cap / 16u; q += blockDim.x) {
+            uint4 v;
+            v.x = v.y = v.z = v.w = 0xFFFFFFFFu;
+            if (q * 16u < len) {
+                v = row[q];
+                v.x = traj_keep(v.x, q * 16u, len);
+                v.y = traj_keep(v.y, q * 16u + 4u, len);
+                v.z = traj_keep(v.z, q * 16u + 8u, len);
+                v.w = traj_keep(v.w, q * 16u + 12u, len);
+            }
+            out[q] = v;
+        }
+    }
+}
+
+hipError_t pk_launch_traj_record(const PkTrajArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(pk_traj_record_kernel, dim3((a.env1 - a.env0 + 255u) / 256u), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t pk_launch_traj_reset(const PkTrajArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(pk_traj_reset_kernel, dim3((a.env1 - a.env0 + 255u) / 256u), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t pk_launch_traj_mark(const PkTrajArgs& a, hipStream_t s) {
+    const u32 items = a.ids ? a.items : a.env1 - a.env0;
+    hipLaunchKernelGGL(pk_traj_mark_kernel, dim3((items + 255u) / 256u), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t pk_launch_traj_move(const PkTrajArgs& a, hipStream_t s) {
+    const u32 grid = a.items < 65536u ? (a.items ? a.items : 1u) : 65536u;
+    hipLaunchKernelGGL(pk_traj_move_kernel, dim3(grid), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t pk_launch_traj_get(const PkTrajArgs& a, hipStream_t s) {
+    const u32 items = a.env1 - a.env0;
+    hipLaunchKernelGGL(pk_traj_get_kernel, dim3(items < 65536u ? items : 65536u), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

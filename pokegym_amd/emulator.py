@@ -299,6 +299,103 @@ class BatchedEmulator:
         return {"used": int(used.value), "overflow": int(overflow.value), "keys": keys, "scores": scores,
                 "lengths": lengths, "visits": visits, "picks": picks}
 
+    # -- action trajectories (stream-ordered except enable) -------------------------------
+    def traj_enable(self):
+        """Record every env's actions from here on (pk_traj_enable; once, synchronous).  Call it
+        before the first step: an env that has already stepped is flagged PK_TRAJ_BROKEN until
+        its next reloading reset."""
+        check(self._L.pk_traj_enable(self._h), "pk_traj_enable")
+
+    @property
+    def traj_capacity(self) -> int:
+        """Bytes of a trajectory row, 0 without trajectories."""
+        return int(self._L.pk_traj_capacity(self._h))
+
+    def _traj_read(self, fn, what: str, first: int, count: int, rows: int, lo: int):
+        origin = torch.full((rows,), -1, dtype=torch.int32, device=self.device)
+        length = torch.zeros(rows, dtype=torch.int32, device=self.device)
+        flags = torch.zeros(rows, dtype=torch.uint8, device=self.device)
+        actions = torch.full((rows, max(self.traj_capacity, 1)), 0xFF, dtype=torch.uint8, device=self.device)
+        check(fn(self._h, first, count, *(ctypes.c_void_p(t.data_ptr()) for t in (origin, length, flags, actions)),
+                 self._stream()), what)
+        sl = slice(lo, lo + count)
+        return {"origin": origin[sl], "length": length[sl], "flags": flags[sl], "actions": actions[sl]}
+
+    def trajectories(self, env0: int = 0, count: int | None = None) -> dict:
+        """The trajectories of envs [env0, env0 + count) (pk_traj_get, on the current stream; the
+        range follows step_range's rule) as device tensors over the range: origin int32 (the slot
+        the episode started from, -1 = the template), length int32, flags uint8 (PK_TRAJ_*) and
+        actions uint8 (count, traj_capacity), 0xFF from the length on."""
+        count = self.n - env0 if count is None else count
+        return self._traj_read(self._L.pk_traj_get, "pk_traj_get", env0, count, self.n, env0)
+
+    def bank_trajectories(self, slot0: int, count: int) -> dict:
+        """The trajectory parts of bank slots [slot0, slot0 + count) (pk_bank_traj_get), as
+        trajectories() returns them; a slot without an episode has flags PK_TRAJ_EMPTY."""
+        return self._traj_read(self._L.pk_bank_traj_get, "pk_bank_traj_get", slot0, count, max(int(count), 1), 0)
+
+    def replay(self, origins, actions, lengths, slots_out, flags=None, envs=None):
+        """Rebuild episodes from their trajectories: trajectory i (origin origins[i], the first
+        lengths[i] bytes of actions[i]) is replayed on env envs[i] (default: env i) and checkpointed
+        into bank slot slots_out[i] right after its last action — at length 0 right after the reset.
+        The slot then holds the machine state and the episode bookkeeping the recorded env had.
+
+        The listed envs are reset from their origins (-1 = the template), so this handle's bank
+        must hold the origin slots with the content the recording handle's had; then EVERY env of
+        the handle is stepped max(lengths) times, finished and unlisted envs with action 8 (no
+        button) — use a handle of its own.  Needs traj_enable() and bank_enable_episodes() on
+        this handle.  Raises ValueError for a trajectory with flags (broken or overflowed), and —
+        after the reset — when the reset did not reload the machine (reward=True without
+        reload_on_reset and the env had been reset before) or an origin slot was rejected.
+        Synchronous (it reads the reset's result back)."""
+        origins = np.asarray(origins, np.int32).reshape(-1)
+        lengths = np.asarray(lengths, np.int64).reshape(-1)
+        slots_out = np.asarray(slots_out, np.int32).reshape(-1)
+        k = len(origins)
+        envs = np.arange(k) if envs is None else np.asarray(envs, np.int64).reshape(-1)
+        if not (len(lengths) == len(slots_out) == len(envs) == len(actions) == k):
+            raise ValueError("replay: origins, actions, lengths, slots_out and envs must have one entry per trajectory")
+        if flags is not None and np.asarray(flags).reshape(-1).any():
+            raise ValueError("replay: a trajectory is flagged broken or overflowed; its actions do not determine its state")
+        if k == 0:
+            return
+        if len(set(envs.tolist())) != k or envs.min() < 0 or envs.max() >= self.n:
+            raise ValueError("replay: envs must be distinct env indices of this handle")
+        if not self.traj_capacity:
+            raise ValueError("replay: the handle needs traj_enable() to verify its resets")
+        steps = int(lengths.max())
+        acts = np.full((steps, self.n), 8, np.uint8)
+        for i in range(k):
+            a = np.asarray(actions[i].cpu() if isinstance(actions[i], torch.Tensor) else actions[i], np.uint8).reshape(-1)
+            if lengths[i] < 0 or lengths[i] > len(a):
+                raise ValueError(f"replay: trajectory {i} has fewer than {lengths[i]} actions")
+            acts[:lengths[i], envs[i]] = a[:lengths[i]]
+
+        def per_env(values, fill, dtype, which=slice(None)):
+            full = np.full(self.n, fill, dtype)
+            full[envs[which]] = values
+            return torch.from_numpy(full).to(self.device)
+
+        mask = per_env(1, 0, np.uint8)
+        if (origins >= 0).any():
+            self.reset_from(per_env(origins, -1, np.int32), mask)
+        else:
+            self.reset(mask)
+        got = self.trajectories()
+        got_flags, got_origin = got["flags"].cpu().numpy()[envs], got["origin"].cpu().numpy()[envs]
+        if got_flags.any():
+            raise ValueError("replay: the resets of this handle do not reload the machine (reward=True without "
+                             "reload_on_reset, envs already reset): nothing to replay from")
+        if (got_origin != origins).any():
+            raise ValueError("replay: an origin slot is empty or out of range on this handle")
+        acts = torch.from_numpy(acts).to(self.device)
+        for t in range(steps + 1):
+            at = np.nonzero(lengths == t)[0]
+            if len(at):
+                self.bank_checkpoint(per_env(slots_out[at], -1, np.int32, at))
+            if t < steps:
+                self.step(acts[t])
+
     def set_episode_params(self, max_episode_steps: int, reward_scale: float):
         """Episode length and reward scale of the following steps (Environment.reset's arguments,
         environment.py:1233, :1258-1259); call before the reset they belong to."""

@@ -245,7 +245,8 @@ class VecEnv:
                  reload_on_reset: bool = False, env_offset: int = 0, log_interval: int = 128, emulator=None,
                  heatmap: bool = False, reward: bool = True, power_on: bool = False, batch_size: int | None = None,
                  state_pool=None, pool_seed: int = 0, bank_slots: int = 0, bank_episodes: bool = False,
-                 fork_slots: int = 0, archive_cells: int = 0, archive_seed: int = 0, archive_shift: int = 0):
+                 fork_slots: int = 0, archive_cells: int = 0, archive_seed: int = 0, archive_shift: int = 0,
+                 record_trajectories: bool = False):
         """reward=False: the screen-obs env of configs[3] — obs is the (144, 160) u8 screen, rewards are
         0 and episodes end at max_episode_steps.  power_on=True starts (and resets) every env from
         the cartridge's power-on state instead of a savestate.
@@ -270,7 +271,14 @@ class VecEnv:
         archive_explore(mask) resumes envs from cells drawn by visit count with archive_seed;
         archive_shift is cell_keys()'s coordinate shift.  Both are calls of the training loop between
         steps: the auto-reset path does not explore, and the archive is not driven per sub-batch
-        on the sub-batch streams."""
+        on the sub-batch streams.
+
+        record_trajectories=True records every env's actions since its last reset on the device
+        (pk_traj_enable): trajectory(env), and with bank_episodes slot_trajectory(slot) and
+        archive_trajectory(cell), return the action list that reaches a state and the slot it starts
+        from — a demonstration, and with BatchedEmulator.replay() the way to rebuild a slot or a
+        whole archive after a restart.  Checkpoints, resumes, forks and the archive carry the lists
+        along.  Without it nothing is allocated or launched."""
         self.batch_size = batch_size or num_envs
         if num_envs % self.batch_size:
             raise ValueError("batch_size must divide num_envs")
@@ -331,6 +339,9 @@ class VecEnv:
         # savestate bank: the pool's states in slots [0, pool_size), bank_slots free ones after them
         self.pool_size = 0
         self._slots = self._pool_gen = None
+        self.record_trajectories = bool(record_trajectories)
+        if self.record_trajectories:
+            self.emu.traj_enable()
         self.fork_slots = int(fork_slots)
         self._cap_lg = _seen_cap_log2(getattr(emulator, "max_episode_steps", 20480))
         self._fork0 = 0             # first scratch slot of fork()
@@ -576,6 +587,42 @@ class VecEnv:
         if self._arch_out is None:
             raise RuntimeError("VecEnv(archive_cells=...) keeps the archive")
         return self.emu.archive_read()
+
+    @staticmethod
+    def _trajectory(d: dict, i: int) -> dict:
+        """Row i of a trajectories() result as host values (synchronises)."""
+        n = int(d["length"][i])
+        return {"origin": int(d["origin"][i]), "actions": d["actions"][i, :n].cpu().numpy().copy(),
+                "replayable": int(d["flags"][i]) == 0}
+
+    def trajectory(self, env: int) -> dict:
+        """How env got where it is: {"origin": the bank slot its episode started from (-1 = the
+        template state), "actions": uint8 array of every action since, "replayable": whether resetting
+        from origin and stepping through actions rebuilds the env exactly (False after load_state,
+        load_from_bank, a RAM write, a reset that kept the machine, or a step past the capacity)}.
+        Needs record_trajectories=True; waits for the sub-batch streams and syncs the host."""
+        if not self.record_trajectories:
+            raise RuntimeError("VecEnv(record_trajectories=True) records trajectories")
+        self._join_streams()
+        p = self.phys(int(env))
+        g0 = p // 64 * 64
+        return self._trajectory(self.emu.trajectories(g0, min(64, self.emu.n - g0)), p - g0)
+
+    def slot_trajectory(self, slot: int) -> dict:
+        """trajectory() of the episode checkpointed in a bank slot; a slot that holds no episode is
+        origin -1, no actions, not replayable."""
+        if not self.record_trajectories:
+            raise RuntimeError("VecEnv(record_trajectories=True) records trajectories")
+        self._join_streams()
+        return self._trajectory(self.emu.bank_trajectories(int(slot), 1), 0)
+
+    def archive_trajectory(self, cell: int) -> dict:
+        """trajectory() of the best episode the archive keeps for a cell."""
+        if self._arch_out is None:
+            raise RuntimeError("VecEnv(archive_cells=...) keeps the archive")
+        if not 0 <= int(cell) < self.archive_cells:
+            raise ValueError("archive_trajectory: no such cell")
+        return self.slot_trajectory(self._arch0 + int(cell))
 
     def _range(self, b: int) -> slice:
         return slice(b * self.batch_size, (b + 1) * self.batch_size)
