@@ -35,6 +35,8 @@
  *                    kept in bank slots, and envs resumed from cells drawn by visit count
  *   pk_traj_enable / pk_traj_get / pk_bank_traj_get   no reference equivalent: the actions of every
  *                    episode, recorded per env and carried through checkpoints, resumes and the archive
+ *   pk_archive_pack / pk_archive_merge   no reference equivalent: an archive's cells as records and
+ *                    whole-slot payloads, and their merge into the archive of another handle
  * With PK_F_REWARD, pk_step also runs the reward stack of Environment.step
  * (environment.py:1338-1612) and pk_reset follows Environment.reset (:1233-1334).
  */
@@ -47,7 +49,7 @@
 extern "C" {
 #endif
 
-#define PK_ABI_VERSION 10
+#define PK_ABI_VERSION 11
 #define PK_STATE_V9_BYTES 142610u
 #define PK_SCREEN_ROWS 144u
 #define PK_SCREEN_COLS 160u
@@ -391,6 +393,89 @@ int pk_traj_get(pk_handle* h, uint32_t env0, uint32_t count, int32_t* origin_dev
                 uint8_t* flags_dev, uint8_t* actions_dev, void* stream);
 int pk_bank_traj_get(pk_handle* h, uint32_t slot0, uint32_t count, int32_t* origin_dev, uint32_t* len_dev,
                      uint8_t* flags_dev, uint8_t* actions_dev, void* stream);
+
+/* Archive exchange: cells leave a handle as records and payloads and enter another handle's archive
+ * by a merge — between the GPUs of a run (one handle per GPU), or to and from a file.
+ *
+ * A record (pk_xrec) is a cell's bookkeeping.  A payload is the cell's whole slot as
+ * pk_archive_payload_bytes() linear bytes, every part at a 16-byte-aligned offset, in this order:
+ *   machine part   RAM image | 20 register words | 3 x 144 latch words | 144 x 160 screen
+ *   episode part   68 record words | seen table (normalised tags) | visited mask | cut coordinates
+ *   trajectory     {origin, flags, 0, 0} | action row at its capacity     (handles with pk_traj_enable)
+ * The total is a multiple of 16 and depends only on the handle's geometry, which
+ * pk_archive_format() names: payload layout version << 24 | trajectories << 23 | cap_log2 << 16 |
+ * the low 16 bits of the RAM image size.  Handles exchange cells only when their formats are equal;
+ * both values change when pk_set_episode_params grows the seen set.  A slot's content does not
+ * depend on the handle (dense image, normalised registers and seen tags, linear action row), so a
+ * merged slot is the source slot, byte for byte.  The trajectory origin is copied verbatim: it names
+ * a slot of the SOURCE's bank, so keeping the state pools of exchanging handles identical is the
+ * caller's job.
+ *
+ * pk_archive_exchange_enable (synchronous): once per handle, needs an archive.  It allocates three
+ * words per cell (sent_visits, sent_picks, dirty; all 0) and the scratch of pk_archive_merge, which
+ * therefore never allocates for up to 65,536 records.  On failure the handle is unchanged.  A
+ * handle that never calls it makes exactly the launches and allocations it made before; on it
+ * pk_archive_pack / pk_archive_merge fail with a negative code and change nothing, and
+ * pk_archive_payload_bytes is 0.  After it, pk_archive_update sets dirty[c] whenever a winner
+ * replaces cell c's record — the only change on an existing path.  Records made before the call are
+ * not dirty: a full pack ships them, a delta pack only their counts.
+ *
+ * pk_archive_pack (stream-ordered, never a host sync): cells c = cell0 .. cell0 + count - 1 in
+ * order, record i = c - cell0 into rec_dev[i] (device pk_xrec[count], 16-byte aligned).
+ *   - c >= the cells in use: key UINT64_MAX, zeros elsewhere, payload -1.
+ *   - otherwise key, score and length are the cell's record, format this handle's.
+ *   - flags == 0: visits and picks are the cell's full counts; every cell gets a payload, numbered
+ *     0, 1, ... in ascending cell order until max_payloads are given, later cells get -1.  The
+ *     archive is not changed in any way.
+ *   - PK_XCHG_DELTA: visits = visits[c] - sent_visits[c] and then sent_visits[c] = visits[c], picks
+ *     likewise (mod 2^32): what this handle counted itself since the last delta pack.  A cell gets
+ *     a payload only if dirty[c] is set, in ascending cell order until max_payloads are given;
+ *     those cells' dirty is cleared, the remaining dirty cells stay dirty (payload -1 this time).
+ * Payload k is written to payload_dev + k * pk_archive_payload_bytes() (16-byte aligned; NULL only
+ * with max_payloads == 0); *n_payloads_dev (optional device u32) receives the number written.
+ * cell0 + count <= pk_archive_cells, count >= 1.
+ *
+ * pk_archive_merge (stream-ordered, never a host sync, no allocation): n_records in 1..65536.  The
+ * result is the one of walking the records i = 0 .. n_records - 1 in ascending order:
+ *   - a record with key UINT64_MAX is skipped;
+ *   - a record whose format differs from this handle's, whose payload is >= n_payloads or whose
+ *     score is NaN is a reject: ignored, and counted in the bank's reject counter;
+ *   - if the key has no cell: with a payload and a free cell the record gets the next free cell
+ *     (visits = picks = 0, no record yet); otherwise (no payload, or the archive is full) overflow
+ *     rises by one and the record does nothing more;
+ *   - visits[c] += rec.visits, picks[c] += rec.picks, and sent_visits[c] / sent_picks[c] rise by the
+ *     same amounts, so counts that came from elsewhere are never sent on (all sums mod 2^32);
+ *   - a record with a payload becomes the cell's record, and the call's winner of the cell, when
+ *     the cell has no record, its score is greater, or its score is equal and its length less
+ *     (pk_archive_update's rules: a stored record only yields to a strictly better one, ties
+ *     inside a call go to the lower record index).
+ * A merge never sets dirty: records that came from elsewhere are not sent on by a later delta pack.
+ * Every winner's payload is then written into slot slot0 + c, all parts, and the slot is marked
+ * filled, with an episode part: pk_bank_get, pk_bank_traj_get and a pk_bank_resume plus continuation
+ * from that slot equal those of the source slot, bit for bit.  cell_out_dev (optional device
+ * i32[n_records]) receives c for the winner of cell c and -1 for every other record.  A negative
+ * payload is "no payload".  payload_dev may be NULL only with n_payloads == 0.
+ *
+ * Bad arguments (a range past pk_archive_cells, a NULL rec_dev, a misaligned pointer, n_records
+ * out of range) are a negative return code, never a fault.  Everything observable is the same
+ * from run to run, as for the rest of the archive, and the concurrency rule is the archive's: the
+ * caller orders the calls that touch it. */
+#define PK_XCHG_DELTA 1u
+typedef struct pk_xrec {           /* 48 bytes, 16-byte aligned */
+    uint64_t key;
+    double score;
+    uint32_t length, visits, picks;
+    int32_t payload;               /* row of the payload array, -1 = none */
+    uint32_t format;               /* pk_archive_format() of the packing handle */
+    uint32_t reserved[3];          /* 0 */
+} pk_xrec;
+int pk_archive_exchange_enable(pk_handle* h);
+uint64_t pk_archive_payload_bytes(const pk_handle* h);
+uint32_t pk_archive_format(const pk_handle* h);
+int pk_archive_pack(pk_handle* h, uint32_t flags, uint32_t cell0, uint32_t count, uint32_t max_payloads,
+                    pk_xrec* rec_dev, uint8_t* payload_dev, uint32_t* n_payloads_dev, void* stream);
+int pk_archive_merge(pk_handle* h, const pk_xrec* rec_dev, uint32_t n_records, const uint8_t* payload_dev,
+                     uint32_t n_payloads, int32_t* cell_out_dev, void* stream);
 
 /* Emulated instructions executed by the last pk_step, summed over envs (synchronous). */
 int pk_last_instr_count(pk_handle* h, uint64_t* out);

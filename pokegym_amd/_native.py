@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # PK_LIB selects an alternative in-tree build (A/B kernel experiments); default: lib/libpokegym_amd.so
 LIB_PATH = os.environ.get("PK_LIB") or os.path.join(HERE, "lib", "libpokegym_amd.so")
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 PK_F_RENDER = 1
 PK_F_REWARD = 2
 PK_F_RELOAD_ON_RESET = 4
@@ -20,6 +20,7 @@ PK_F_HEATMAP = 8
 PK_TRAJ_BROKEN = 1
 PK_TRAJ_OVERFLOW = 2
 PK_TRAJ_EMPTY = 4
+PK_XCHG_DELTA = 1
 HEAT_SHAPE = (444, 436)
 OBS_SHAPE = (72, 80, 4)
 # PK_ERR_* -> the exception the reference raises at that point (include/pokegym_amd.h)
@@ -40,7 +41,9 @@ EXPORTS = ("pk_create", "pk_destroy", "pk_last_error", "pk_abi_version", "pk_res
            "pk_bank_enable_episodes", "pk_bank_has_episodes", "pk_bank_checkpoint", "pk_bank_resume",
            "pk_archive_create", "pk_archive_cells", "pk_cell_keys", "pk_archive_update", "pk_archive_explore",
            "pk_archive_read",
-           "pk_traj_enable", "pk_traj_capacity", "pk_traj_get", "pk_bank_traj_get")
+           "pk_traj_enable", "pk_traj_capacity", "pk_traj_get", "pk_bank_traj_get",
+           "pk_archive_exchange_enable", "pk_archive_payload_bytes", "pk_archive_format", "pk_archive_pack",
+           "pk_archive_merge")
 
 
 class PkConfig(ctypes.Structure):
@@ -56,6 +59,20 @@ class PkConfig(ctypes.Structure):
         ("flags", ctypes.c_uint32),
         ("max_episode_steps", ctypes.c_uint32),
         ("reward_scale", ctypes.c_double),
+    ]
+
+
+class PkXrec(ctypes.Structure):
+    """pk_xrec: one cell of a packed archive (48 bytes)."""
+    _fields_ = [
+        ("key", ctypes.c_uint64),
+        ("score", ctypes.c_double),
+        ("length", ctypes.c_uint32),
+        ("visits", ctypes.c_uint32),
+        ("picks", ctypes.c_uint32),
+        ("payload", ctypes.c_int32),
+        ("format", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32 * 3),
     ]
 
 
@@ -111,6 +128,7 @@ def bind(L):
     bind_v8(L)
     bind_v9(L)
     bind_v10(L)
+    bind_v11(L)
 
 
 def bind_v2(L):
@@ -186,6 +204,19 @@ def bind_v10(L):
     L.pk_traj_capacity.restype = u32
     L.pk_traj_get.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp]
     L.pk_bank_traj_get.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp]
+
+
+def bind_v11(L):
+    """argtypes of the archive exchange (ABI v11; shared with the host-simulation test build)."""
+    vp = ctypes.c_void_p
+    u32 = ctypes.c_uint32
+    L.pk_archive_exchange_enable.argtypes = [vp]
+    L.pk_archive_payload_bytes.argtypes = [vp]
+    L.pk_archive_payload_bytes.restype = ctypes.c_uint64
+    L.pk_archive_format.argtypes = [vp]
+    L.pk_archive_format.restype = u32
+    L.pk_archive_pack.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp, vp]
+    L.pk_archive_merge.argtypes = [vp, vp, u32, vp, u32, vp, vp]
 
 
 def check(rc: int, what: str):

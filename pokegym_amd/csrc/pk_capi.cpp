@@ -44,6 +44,9 @@ hipError_t pk_launch_bank_copy(const PkBankArgs& a, hipStream_t s);
 hipError_t pk_launch_ep_move(const PkEpArgs& a, hipStream_t s);
 hipError_t pk_launch_arch_update(const PkArchArgs& a, hipStream_t s);
 hipError_t pk_launch_arch_draw(const PkArchArgs& a, hipStream_t s);
+hipError_t pk_launch_arch_merge(const PkArchArgs& a, hipStream_t s);
+hipError_t pk_launch_xchg_pack(const PkPackArgs& p, hipStream_t s);
+hipError_t pk_launch_xchg_move(const PkXchgArgs& x, bool pack, hipStream_t s);
 hipError_t pk_launch_arch_out(const PkArchArgs& a, hipStream_t s);
 hipError_t pk_launch_cell_keys(const uint8_t* mem, uint32_t sh, uint32_t shift, uint64_t* keys, uint32_t env0,
                                uint32_t env1, hipStream_t s);
@@ -309,6 +312,12 @@ struct pk_handle {
     uint8_t* a_fix = nullptr;
     uint8_t* a_ones = nullptr;
     uint8_t* a_zero = nullptr;
+    // archive exchange (pk_archive_exchange_enable), null without it: the per-cell sent / dirty words
+    // with the per-record words of a merge, and a merge's own cleared-to-ones / cleared-to-zero blocks,
+    // sized for PK_XCHG_MAX_RECORDS records
+    uint8_t* x_fix = nullptr;
+    uint8_t* x_ones = nullptr;
+    uint8_t* x_zero = nullptr;
     // action trajectories (pk_traj_enable; pk_reward.h PkTrajArgs), traj_cap = 0 without them: the
     // envs' rows, origins and flags, and the slots' while the bank carries episode parts
     uint32_t traj_cap = 0;
@@ -359,7 +368,7 @@ void pk_destroy(pk_handle* h) {
                     h->lists, h->dbg, h->info, h->info_flag, h->heat, h->info_bits, h->bank_slot_s, h->slot_bank_s,
                     h->b_mem, h->b_regs, h->b_lat, h->b_screen, h->b_filled, h->b_rejects, h->b_lists, h->b_src,
                     h->e_fields, h->e_seen, h->e_mask, h->e_cutc, h->b_ep_filled, h->a_fix, h->a_ones, h->a_zero,
-                    h->t_act, h->t_origin, h->t_flags, h->bt_act, h->bt_origin, h->bt_flags};
+                    h->x_fix, h->x_ones, h->x_zero, h->t_act, h->t_origin, h->t_flags, h->bt_act, h->bt_origin, h->bt_flags};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     delete h;
@@ -1553,6 +1562,11 @@ static PkArchArgs arch_args(pk_handle* h, uint32_t env0, uint32_t env1, uint32_t
     a.i_mask = h->arch_imask; a.s_mask = ssize - 1u;
     a.n_cells = K; a.slot0 = h->arch_slot0;
     a.env0 = env0; a.env1 = env1;
+    if (h->x_fix) {   // an update marks the cells whose record it replaces
+        a.x_sent_visits = (uint32_t*)h->x_fix;
+        a.x_sent_picks = a.x_sent_visits + K;
+        a.x_dirty = a.x_sent_picks + K;
+    }
     return a;
 }
 
@@ -1651,6 +1665,177 @@ int pk_archive_read(pk_handle* h, uint32_t* used, uint64_t* keys, double* scores
     if (lengths) HIPCHK(hipMemcpy(lengths, a.a_len, K * 4, hipMemcpyDeviceToHost));
     if (visits) HIPCHK(hipMemcpy(visits, a.a_visits, K * 4, hipMemcpyDeviceToHost));
     if (picks) HIPCHK(hipMemcpy(picks, a.a_picks, K * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- archive exchange ---------------------------------------------------------------------------
+
+uint32_t pk_archive_format(const pk_handle* h) {
+    if (!h) return 0;
+    return (PK_XCHG_VERSION << 24) | (h->traj_cap ? 1u << 23 : 0u) | ((h->cap_log2 & 0x7Fu) << 16) | (PK_PHYS & 0xFFFFu);
+}
+
+// The payload layout: the parts of a slot in their fixed order, each an array of the handle with
+// one row per slot.  Machine part: RAM image, registers, latches, screen; episode part: record
+// words, seen table, visited mask, cut coordinates; on a handle with trajectories the piece
+// {origin, flags, 0, 0} and the action row.  Every row size is a multiple of 16.
+static PkXchgArgs xchg_args(const pk_handle* h) {
+    static_assert(PK_PHYS % 16u == 0u && (PK_BANK_REGS * 4u) % 16u == 0u && (3u * PK_ROWS * 4u) % 16u == 0u &&
+                  PK_SCREEN % 16u == 0u && (PK_EP_WORDS * 4u) % 16u == 0u && (PK_MASK_WORDS * 4u) % 16u == 0u &&
+                  (PK_CUTC_CAP * 4u) % 16u == 0u, "payload parts are whole 16-byte pieces");
+    PkXchgArgs x;
+    memset(&x, 0, sizeof x);
+    uint32_t n = 0, off = 0;
+    auto part = [&](void* base, uint32_t bytes) {
+        x.base[n] = (uint8_t*)base;
+        x.stride[n] = bytes;
+        x.off16[n] = off;
+        off += bytes / 16u;
+        n++;
+    };
+    part(h->b_mem, PK_PHYS);
+    part(h->b_regs, PK_BANK_REGS * 4u);
+    part(h->b_lat, 3u * PK_ROWS * 4u);
+    part(h->b_screen, PK_SCREEN);
+    part(h->e_fields, PK_EP_WORDS * 4u);
+    part(h->e_seen, 4u << h->cap_log2);
+    part(h->e_mask, PK_MASK_WORDS * 4u);
+    part(h->e_cutc, PK_CUTC_CAP * 4u);
+    x.head16 = PK_ARCH_NONE;
+    if (h->traj_cap) {
+        x.head16 = off;
+        part(nullptr, 16u);
+        part(h->bt_act, h->traj_cap);
+    }
+    static_assert(PK_XCHG_MAX_PARTS >= 10u, "payload parts");
+    x.nparts = n;
+    x.off16[n] = off;
+    x.pay16 = off;
+    x.bt_origin = h->bt_origin; x.bt_flags = h->bt_flags;
+    x.b_filled = h->b_filled; x.b_ep_filled = h->b_ep_filled;
+    x.slot0 = h->arch_slot0;
+    return x;
+}
+
+uint64_t pk_archive_payload_bytes(const pk_handle* h) {
+    if (!h || !h->x_fix) return 0;
+    return (uint64_t)xchg_args(h).pay16 * 16u;
+}
+
+// the exchange blocks: x_fix = [sent_visits | sent_picks | dirty][n_cells] [tgt | x_cell | x_pay][R]
+// u32, flag u8[R]; x_ones = [c_le[n_cells] | s_key[S] | s_le[S]] u64, s_first u32[S]; x_zero = x_cnt
+// (16 bytes), [c_max[n_cells] | s_max[S]] u64, [s_cnt | s_vis | s_pick | s_cell][S] u32 — R the most
+// records of a merge, S the scratch table of a call (allocated for R)
+static PkArchArgs xchg_arch_args(pk_handle* h, uint32_t n_records, uint32_t ssize) {
+    PkArchArgs a = arch_args(h, 0, n_records, 64);
+    const uint32_t K = h->arch_cells, R = PK_XCHG_MAX_RECORDS;
+    uint32_t* w = a.x_dirty + K;
+    a.tgt = w; w += R;
+    a.x_cell = w; w += R;
+    a.x_pay = w; w += R;
+    a.flag = (uint8_t*)w;
+    a.map = nullptr;
+    uint64_t* q = (uint64_t*)h->x_ones;
+    a.c_le = q; q += K;
+    a.s_key = q; q += ssize;
+    a.s_le = q; q += ssize;
+    a.s_first = (uint32_t*)q;
+    q = (uint64_t*)h->x_zero;
+    a.x_cnt = (uint32_t*)q; q += 2;
+    a.c_max = q; q += K;
+    a.s_max = q; q += ssize;
+    a.s_cnt = (uint32_t*)q;
+    a.s_vis = a.s_cnt + ssize;
+    a.s_pick = a.s_vis + ssize;
+    a.s_cell = a.s_pick + ssize;
+    a.s_mask = ssize - 1u;
+    a.format = pk_archive_format(h);
+    return a;
+}
+
+static size_t xchg_ones_bytes(uint32_t cells, uint32_t ssize) { return ((size_t)cells + 2ull * ssize) * 8 + (size_t)ssize * 4; }
+// the cleared part of x_zero: everything but s_cell, which the rank phase writes before it is read
+static size_t xchg_zero_bytes(uint32_t cells, uint32_t ssize) { return 16 + ((size_t)cells + ssize) * 8 + 3ull * ssize * 4; }
+
+int pk_archive_exchange_enable(pk_handle* h) {
+    if (!h) return fail(-EINVAL, "null handle");
+    if (!h->arch_cells) return fail(-ENOENT, "the handle has no archive (pk_archive_create)");
+    if (h->x_fix) return fail(-EEXIST, "the archive already has its exchange words");
+    HIPCHK(hipSetDevice(h->device));
+    const uint32_t K = h->arch_cells, R = PK_XCHG_MAX_RECORDS, S = pow2_at_least(2ull * R);
+    const size_t fix = (3ull * K + 3ull * R) * 4 + R, ones = xchg_ones_bytes(K, S), zero = xchg_zero_bytes(K, S) + (size_t)S * 4;
+    uint8_t *pf = nullptr, *po = nullptr, *pz = nullptr;
+    hipError_t e = hipMalloc((void**)&pf, fix);
+    if (e == hipSuccess) e = hipMalloc((void**)&po, ones);
+    if (e == hipSuccess) e = hipMalloc((void**)&pz, zero);
+    if (e == hipSuccess) e = hipMemset(pf, 0, fix);
+    if (e == hipSuccess) e = hipMemset(pz, 0, zero);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        void* ptrs[] = {pf, po, pz};
+        for (void* p : ptrs)
+            if (p) (void)hipFree(p);
+        (void)hipGetLastError();
+        return fail(-ENOMEM, "exchange words of %u cells (%zu bytes): %s", K, fix + ones + zero, hipGetErrorString(e));
+    }
+    h->x_fix = pf; h->x_ones = po; h->x_zero = pz;
+    return 0;
+}
+
+static int check_xchg(pk_handle* h) {
+    if (!h) return fail(-EINVAL, "null handle");
+    if (!h->arch_cells) return fail(-ENOENT, "the handle has no archive (pk_archive_create)");
+    if (!h->x_fix) return fail(-ENOENT, "the archive has no exchange words (pk_archive_exchange_enable)");
+    return 0;
+}
+
+int pk_archive_pack(pk_handle* h, uint32_t flags, uint32_t cell0, uint32_t count, uint32_t max_payloads, pk_xrec* rec,
+                    uint8_t* payload, uint32_t* n_payloads, void* stream) {
+    int rc;
+    if ((rc = check_xchg(h))) return rc;
+    if (flags & ~PK_XCHG_DELTA) return fail(-EINVAL, "unknown flags 0x%x", flags);
+    if (count == 0 || (uint64_t)cell0 + count > h->arch_cells)
+        return fail(-EINVAL, "cells [%u, +%u) are not inside the archive's %u", cell0, count, h->arch_cells);
+    if (!rec || ((uintptr_t)rec & 15u)) return fail(-EINVAL, "rec_dev is required, 16-byte aligned");
+    if ((!payload && max_payloads) || ((uintptr_t)payload & 15u))
+        return fail(-EINVAL, "payload_dev is required for max_payloads > 0, 16-byte aligned");
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    PkPackArgs p;
+    memset(&p, 0, sizeof p);
+    p.a = xchg_arch_args(h, 0, 64);
+    p.out = rec; p.n_payloads_out = n_payloads;
+    p.cell0 = cell0; p.count = count; p.max_payloads = max_payloads; p.delta = flags & PK_XCHG_DELTA;
+    HIPCHK(pk_launch_xchg_pack(p, s));
+    PkXchgArgs x = xchg_args(h);
+    x.payload = payload;
+    x.cnt = p.a.x_cnt; x.cell = p.a.x_cell; x.pay = p.a.x_pay;
+    x.items = count < max_payloads ? count : max_payloads;
+    HIPCHK(pk_launch_xchg_move(x, true, s));
+    return 0;
+}
+
+int pk_archive_merge(pk_handle* h, const pk_xrec* rec, uint32_t n_records, const uint8_t* payload, uint32_t n_payloads,
+                     int32_t* cell_out, void* stream) {
+    int rc;
+    if ((rc = check_xchg(h))) return rc;
+    if (n_records == 0 || n_records > PK_XCHG_MAX_RECORDS) return fail(-EINVAL, "n_records must be 1..%u", PK_XCHG_MAX_RECORDS);
+    if (!rec || ((uintptr_t)rec & 15u)) return fail(-EINVAL, "rec_dev is required, 16-byte aligned");
+    if ((!payload && n_payloads) || ((uintptr_t)payload & 15u))
+        return fail(-EINVAL, "payload_dev is required for n_payloads > 0, 16-byte aligned");
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    const uint32_t S = pow2_at_least(2ull * n_records);
+    PkArchArgs a = xchg_arch_args(h, n_records, S);
+    a.rec = rec; a.n_payloads = n_payloads; a.out = cell_out;
+    HIPCHK(hipMemsetAsync(h->x_ones, 0xFF, xchg_ones_bytes(a.n_cells, S), s));
+    HIPCHK(hipMemsetAsync(h->x_zero, 0, xchg_zero_bytes(a.n_cells, S), s));
+    HIPCHK(pk_launch_arch_merge(a, s));
+    PkXchgArgs x = xchg_args(h);
+    x.payload = const_cast<uint8_t*>(payload);
+    x.cnt = a.x_cnt; x.cell = a.x_cell; x.pay = a.x_pay;
+    x.items = n_records < n_payloads ? n_records : n_payloads;
+    HIPCHK(pk_launch_xchg_move(x, false, s));
     return 0;
 }
 

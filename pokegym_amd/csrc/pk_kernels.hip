@@ -15,6 +15,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "../../include/pokegym_amd.h"
 #include "pk_layout.h"
 #include "pk_render.h"
 
@@ -448,26 +449,54 @@ __device__ static inline bool pk_arch_group(bool todo, u32 t, bool& match, bool&
     return true;
 }
 
-// the words an env brings to an update: whether it takes part, its encoded score and length << 32 | env
-__device__ static inline bool pk_arch_env(const PkArchArgs& A, u32 e, u64& key, u64& enc, u64& le) {
-    if (e >= A.env1 || (A.mask && !A.mask[e])) return false;
-    key = A.keys[e];
-    const double sc = A.scores[e];
-    if (key == PK_ARCH_NOKEY || sc != sc) return false;
+// the words an item brings to an update or a merge: whether it takes part, its encoded score and
+// length << 32 | index.  An item is an env (REC = false) or record e of a merge: its length comes from
+// the record, pay says whether it brings a payload (an env always does: its own state), and reject
+// that it is counted as a reject (a foreign format, a payload row past the array, a NaN score).
+template <bool REC>
+__device__ static inline bool pk_arch_item(const PkArchArgs& A, u32 e, u64& key, u64& enc, u64& le, bool& pay, bool& reject) {
+    pay = true;
+    reject = false;
+    if (e >= A.env1) return false;
+    double sc;
+    u32 len;
+    if (REC) {
+        const pk_xrec& r = A.rec[e];
+        key = r.key;
+        if (key == PK_ARCH_NOKEY) return false;
+        sc = r.score;
+        pay = r.payload >= 0;
+        if (r.format != A.format || (pay && (u32)r.payload >= A.n_payloads) || sc != sc) {
+            reject = true;
+            return false;
+        }
+        len = r.length;
+    } else {
+        if (A.mask && !A.mask[e]) return false;
+        key = A.keys[e];
+        sc = A.scores[e];
+        if (key == PK_ARCH_NOKEY || sc != sc) return false;
+        len = A.time_reg[e];
+    }
     enc = pk_arch_enc(sc);
-    le = ((u64)A.time_reg[e] << 32) | e;
+    le = ((u64)len << 32) | e;
     return true;
 }
 
 // phase 1, thread = env: find the key's cell in the index, else claim a scratch entry for it; count
 // the visit, and bring the score to the target's max word — for a known cell only where it beats
-// the stored record (a better score, or the same score in fewer steps)
+// the stored record (a better score, or the same score in fewer steps).  A merge (REC) adds the
+// record's own visit and pick counts, to the sent words as well; only a record with a payload is a
+// candidate, and for a new key the first such record is the one that makes the cell: what the
+// records of a new key count is settled in phase 2, when that first record is known.  Records
+// seldom share a cell, so a merge skips the wave pre-reduction.
+template <bool REC>
 __global__ void __launch_bounds__(256) pk_arch_claim_kernel(PkArchArgs A) {
     const u32 e = A.env0 + blockIdx.x * blockDim.x + threadIdx.x;
     u64 key = PK_ARCH_NOKEY, enc = 0, le = 0;
     u32 t = PK_ARCH_NONE;
-    bool cand = false;
-    if (pk_arch_env(A, e, key, enc, le)) {
+    bool cand = false, pay, reject;
+    if (pk_arch_item<REC>(A, e, key, enc, le, pay, reject)) {
         const u32 h = (u32)pk_arch_mix(key);
         u32 pos = h & A.i_mask;
         for (u32 p = 0; p <= A.i_mask; p++, pos = (pos + 1u) & A.i_mask) {
@@ -477,7 +506,7 @@ __global__ void __launch_bounds__(256) pk_arch_claim_kernel(PkArchArgs A) {
         }
         if (t != PK_ARCH_NONE) {
             const u64 renc = pk_arch_enc(A.a_score[t]);
-            cand = enc > renc || (enc == renc && (u32)(le >> 32) < A.a_len[t]);
+            cand = pay && (enc > renc || (enc == renc && (u32)(le >> 32) < A.a_len[t]));
         } else {
             pos = h & A.s_mask;
             for (u32 p = 0; p <= A.s_mask; p++, pos = (pos + 1u) & A.s_mask) {
@@ -486,13 +515,33 @@ __global__ void __launch_bounds__(256) pk_arch_claim_kernel(PkArchArgs A) {
                 if (k == PK_ARCH_NOKEY) k = atomicCAS(sk, (ull)PK_ARCH_NOKEY, (ull)key);
                 if (k == PK_ARCH_NOKEY || k == key) {
                     t = A.n_cells + pos;
-                    cand = true;
+                    cand = pay;
                     break;
                 }
             }
         }
     }
     if (e < A.env1) A.tgt[e] = t;
+    if (REC) {
+        if (reject) atomicAdd(A.b_rejects, 1u);
+        if (t == PK_ARCH_NONE) return;
+        if (t < A.n_cells) {
+            const u32 rv = A.rec[e].visits, rp = A.rec[e].picks;
+            if (rv) {
+                atomicAdd(A.a_visits + t, rv);
+                atomicAdd(A.x_sent_visits + t, rv);
+            }
+            if (rp) {
+                atomicAdd(A.a_picks + t, rp);
+                atomicAdd(A.x_sent_picks + t, rp);
+            }
+            if (cand) atomicMax(reinterpret_cast<ull*>(A.c_max + t), (ull)enc);
+        } else if (cand) {
+            atomicMax(reinterpret_cast<ull*>(A.s_max + (t - A.n_cells)), (ull)enc);
+            atomicMin(A.s_first + (t - A.n_cells), e);
+        }
+        return;
+    }
     bool todo = t != PK_ARCH_NONE, match, lead;
     u64 mm;
     for (u32 it = 0; it <= PK_ARCH_PRE; it++) {
@@ -525,19 +574,41 @@ __global__ void __launch_bounds__(256) pk_arch_claim_kernel(PkArchArgs A) {
 }
 
 // phase 2, thread = env: among the envs that hold the target's best score, the least length, then
-// the least env; and flag the env that is the first of a new key
+// the least env; and flag the env that is the first of a new key.  In a merge (REC) the first
+// record of a new key is its first record with a payload: the records before it (or all, when no
+// record of the key has a payload) found no cell and count as overflow, those from it on bring
+// their visits and picks to the entry.
+template <bool REC>
 __global__ void __launch_bounds__(256) pk_arch_best_kernel(PkArchArgs A) {
     const u32 e = A.env0 + blockIdx.x * blockDim.x + threadIdx.x;
     u64 key, enc = 0, le = 0;
-    const u32 t = e < A.env1 ? A.tgt[e] : PK_ARCH_NONE;
-    bool todo = false, match, lead;
+    u32 t = e < A.env1 ? A.tgt[e] : PK_ARCH_NONE;
+    bool todo = false, match, lead, pay, reject;
     if (t != PK_ARCH_NONE) {
-        pk_arch_env(A, e, key, enc, le);
+        pk_arch_item<REC>(A, e, key, enc, le, pay, reject);
         const u32 j = t - A.n_cells;
-        todo = enc == (t < A.n_cells ? A.c_max[t] : A.s_max[j]);
+        if (REC && t >= A.n_cells) {
+            const u32 first = A.s_first[j];
+            if (first == PK_ARCH_NONE || e < first) {
+                atomicAdd(reinterpret_cast<ull*>(A.hdr + PK_AH_OVERFLOW), 1ull);
+                A.tgt[e] = t = PK_ARCH_NONE;
+            } else {
+                atomicAdd(A.s_cnt + j, 1u);
+                atomicAdd(A.s_vis + j, A.rec[e].visits);
+                atomicAdd(A.s_pick + j, A.rec[e].picks);
+            }
+        }
+    }
+    if (t != PK_ARCH_NONE) {
+        const u32 j = t - A.n_cells;
+        todo = pay && enc == (t < A.n_cells ? A.c_max[t] : A.s_max[j]);
         A.flag[e] = t >= A.n_cells && A.s_first[j] == e ? 1 : 0;
     } else if (e < A.env1) {
         A.flag[e] = 0;
+    }
+    if (REC) {
+        if (todo) atomicMin(reinterpret_cast<ull*>(t < A.n_cells ? A.c_le + t : A.s_le + (t - A.n_cells)), (ull)le);
+        return;
     }
     u64 mm;
     for (u32 it = 0; it <= PK_ARCH_PRE; it++) {
@@ -595,27 +666,36 @@ __global__ void __launch_bounds__(256) pk_arch_rank_kernel(PkArchArgs A) {
 }
 
 // phase 4, thread = env: the first env of an accepted new key writes the cell and enters the key
-// into the index; the winner of a target writes the record; every env gets its line of the slot map
+// into the index; the winner of a target writes the record; every env gets its line of the slot map.
+// On a handle with archive exchange an update's winner marks its cell dirty.  A merge (REC) starts a
+// new cell with the counts its records brought, all of them sent words too, lists each winner's
+// cell and payload row for the mover, never touches dirty, and writes cell_out in the map's place.
+template <bool REC>
 __global__ void __launch_bounds__(256) pk_arch_commit_kernel(PkArchArgs A) {
     const u32 e = A.env0 + blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= A.env1) return;
     const u32 t = A.tgt[e];
-    int32_t slot = -1;
+    int32_t slot = -1, cell = -1;
     u64 key, enc, le;
+    bool pay, reject;
     if (t != PK_ARCH_NONE) {
-        pk_arch_env(A, e, key, enc, le);
+        pk_arch_item<REC>(A, e, key, enc, le, pay, reject);
         u32 c = t;
         bool win;
         if (t < A.n_cells) {
-            win = enc == A.c_max[t] && le == A.c_le[t];
+            win = pay && enc == A.c_max[t] && le == A.c_le[t];
         } else {
             const u32 j = t - A.n_cells;
             c = A.s_cell[j];
-            win = c != PK_ARCH_NONE && enc == A.s_max[j] && le == A.s_le[j];
+            win = c != PK_ARCH_NONE && pay && enc == A.s_max[j] && le == A.s_le[j];
             if (c != PK_ARCH_NONE && A.s_first[j] == e) {
                 A.a_key[c] = key;
-                A.a_visits[c] = A.s_cnt[j];
-                A.a_picks[c] = 0;
+                A.a_visits[c] = REC ? A.s_vis[j] : A.s_cnt[j];
+                A.a_picks[c] = REC ? A.s_pick[j] : 0u;
+                if (REC) {
+                    A.x_sent_visits[c] = A.s_vis[j];
+                    A.x_sent_picks[c] = A.s_pick[j];
+                }
                 u32 pos = (u32)pk_arch_mix(key) & A.i_mask;
                 for (u32 p = 0; p <= A.i_mask; p++, pos = (pos + 1u) & A.i_mask) {
                     ull* ik = reinterpret_cast<ull*>(A.i_key + pos);
@@ -628,12 +708,21 @@ __global__ void __launch_bounds__(256) pk_arch_commit_kernel(PkArchArgs A) {
             }
         }
         if (win) {
-            A.a_score[c] = A.scores[e];
+            A.a_score[c] = REC ? A.rec[e].score : A.scores[e];
             A.a_len[c] = (u32)(le >> 32);
             slot = (int32_t)(A.slot0 + c);
+            cell = (int32_t)c;
+            if (REC) {
+                const u32 k = atomicAdd(A.x_cnt, 1u);
+                A.x_cell[k] = c;
+                A.x_pay[k] = (u32)A.rec[e].payload;
+            } else if (A.x_dirty) {
+                A.x_dirty[c] = 1u;
+            }
         }
     }
-    A.map[e] = slot;
+    if (!REC) A.map[e] = slot;
+    else if (A.out) A.out[e] = cell;
 }
 
 // explore, one workgroup: the weights of the cells in use (Go-Explore's 1 / sqrt(n + 1) in fixed
@@ -719,10 +808,20 @@ static inline dim3 pk_arch_grid(const PkArchArgs& a) { return dim3((a.env1 - a.e
 
 // phases 1-4 of pk_archive_update; the per-call words are cleared
 hipError_t pk_launch_arch_update(const PkArchArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(pk_arch_claim_kernel, pk_arch_grid(a), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(pk_arch_best_kernel, pk_arch_grid(a), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((pk_arch_claim_kernel<false>), pk_arch_grid(a), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((pk_arch_best_kernel<false>), pk_arch_grid(a), dim3(256), 0, s, a);
     hipLaunchKernelGGL(PK_K1_KERNEL_ARCH_RANK, dim3(1), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(pk_arch_commit_kernel, pk_arch_grid(a), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((pk_arch_commit_kernel<false>), pk_arch_grid(a), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// the same four phases over the records of a pk_archive_merge (a.rec, items [0, a.env1)); leaves the
+// list of winners (x_cnt, x_cell, x_pay) for pk_launch_xchg_move
+hipError_t pk_launch_arch_merge(const PkArchArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL((pk_arch_claim_kernel<true>), pk_arch_grid(a), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((pk_arch_best_kernel<true>), pk_arch_grid(a), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(PK_K1_KERNEL_ARCH_RANK, dim3(1), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((pk_arch_commit_kernel<true>), pk_arch_grid(a), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
@@ -739,5 +838,136 @@ hipError_t pk_launch_arch_out(const PkArchArgs& a, hipStream_t s) {
 
 hipError_t pk_launch_cell_keys(const u8* mem, u32 sh, u32 shift, u64* keys, u32 env0, u32 env1, hipStream_t s) {
     hipLaunchKernelGGL(pk_cell_keys_kernel, dim3((env1 - env0 + 255u) / 256u), dim3(256), 0, s, mem, sh, shift, keys, env0, env1);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// Archive exchange (pk_archive_pack / pk_archive_merge): cells as records and whole-slot payloads.
+
+// pk_archive_pack, one workgroup: the records of cells [cell0, cell0 + count) and, by a scan in cell
+// order like pk_arch_rank_kernel's, the payload rows — every cell in use (full), or the dirty ones
+// (delta), numbered 0, 1, ... until max_payloads are given.  The cells that got a row are listed
+// for the mover.  A delta pack also moves the sent words up to the counts and clears the dirty
+// word of the cells it ships; a full pack writes nothing into the archive.
+#define PK_K1_KERNEL_XCHG_PACK pk_xchg_pack_kernel
+__global__ void __launch_bounds__(256) pk_xchg_pack_kernel(PkPackArgs P) {
+    __shared__ u32 sums[256];
+    const PkArchArgs& A = P.a;
+    const u32 tid = threadIdx.x, chunk = (P.count + 255u) / 256u;
+    const u32 b = tid * chunk < P.count ? tid * chunk : P.count;
+    const u32 end = P.count - b < chunk ? P.count : b + chunk;
+    const u32 used = (u32)A.hdr[PK_AH_USED];
+    u32 s = 0;
+    for (u32 i = b; i < end; i++) {
+        const u32 c = P.cell0 + i;
+        s += c < used && (!P.delta || A.x_dirty[c]) ? 1u : 0u;
+    }
+    sums[tid] = s;
+    __syncthreads();
+    for (u32 o = 1; o < 256u; o <<= 1) {
+        const u32 v = tid >= o ? sums[tid - o] : 0u;
+        __syncthreads();
+        sums[tid] += v;
+        __syncthreads();
+    }
+    u32 r = sums[tid] - s;
+    for (u32 i = b; i < end; i++) {
+        const u32 c = P.cell0 + i;
+        pk_xrec o;
+        memset(&o, 0, sizeof o);
+        o.key = PK_ARCH_NOKEY;
+        o.payload = -1;
+        if (c < used) {
+            const u32 v = A.a_visits[c], p = A.a_picks[c];
+            o.key = A.a_key[c];
+            o.score = A.a_score[c];
+            o.length = A.a_len[c];
+            o.format = A.format;
+            o.visits = v;
+            o.picks = p;
+            bool want = true;
+            if (P.delta) {
+                o.visits = v - A.x_sent_visits[c];
+                o.picks = p - A.x_sent_picks[c];
+                A.x_sent_visits[c] = v;
+                A.x_sent_picks[c] = p;
+                want = A.x_dirty[c] != 0u;
+            }
+            if (want) {
+                if (r < P.max_payloads) {
+                    o.payload = (int32_t)r;
+                    A.x_cell[r] = c;
+                    A.x_pay[r] = r;
+                    if (P.delta) A.x_dirty[c] = 0u;
+                }
+                r++;
+            }
+        }
+        P.out[i] = o;
+    }
+    if (tid == 0) {
+        const u32 n = sums[255] < P.max_payloads ? sums[255] : P.max_payloads;
+        A.x_cnt[0] = n;
+        if (P.n_payloads_out) *P.n_payloads_out = n;
+    }
+}
+
+// The movers, slot -> payload (PACK) and payload -> slot.  A workgroup takes one listed item and a
+// chunk of PK_XCHG_CHUNK 16-byte pieces of its payload; consecutive lanes move consecutive pieces
+// with uint4 loads and stores on both sides (every part of a slot is linear and 16-byte aligned).
+// No LDS, no atomics, no byte traffic besides the two "filled" marks of an unpacked slot.  The work
+// loop runs over the device-built list: nothing scans a slot that does not move.
+template <bool PACK>
+__global__ void __launch_bounds__(256) pk_xchg_move_kernel(PkXchgArgs X) {
+    const u32 chunks = (X.pay16 + PK_XCHG_CHUNK - 1u) / PK_XCHG_CHUNK;
+    const u32 total = X.cnt[0] * chunks;
+    for (u32 w = blockIdx.x; w < total; w += gridDim.x) {
+        const u32 k = w / chunks, q0 = (w - k * chunks) * PK_XCHG_CHUNK;
+        const u32 q1 = X.pay16 - q0 < PK_XCHG_CHUNK ? X.pay16 : q0 + PK_XCHG_CHUNK;
+        const u32 slot = X.slot0 + X.cell[k];
+        uint4* pp = reinterpret_cast<uint4*>(X.payload + (size_t)X.pay[k] * X.pay16 * 16u);
+        for (u32 q = q0 + threadIdx.x; q < q1; q += blockDim.x) {
+            if (q == X.head16) {
+                if (PACK) {
+                    pp[q] = make_uint4((u32)X.bt_origin[slot], X.bt_flags[slot], 0u, 0u);
+                } else {
+                    const uint4 v = pp[q];
+                    X.bt_origin[slot] = (int32_t)v.x;
+                    X.bt_flags[slot] = v.y;
+                }
+                continue;
+            }
+            u8* base = X.base[0];
+            u32 stride = X.stride[0], off = 0;
+#pragma unroll
+            for (u32 p = 1; p < PK_XCHG_MAX_PARTS; p++)
+                if (p < X.nparts && q >= X.off16[p]) {
+                    base = X.base[p];
+                    stride = X.stride[p];
+                    off = X.off16[p];
+                }
+            uint4* sp = reinterpret_cast<uint4*>(base + (size_t)slot * stride) + (q - off);
+            if (PACK) pp[q] = *sp;
+            else *sp = pp[q];
+        }
+        if (!PACK && q0 == 0u && threadIdx.x == 0u) {
+            X.b_filled[slot] = 1;
+            X.b_ep_filled[slot] = 1;
+        }
+    }
+}
+
+hipError_t pk_launch_xchg_pack(const PkPackArgs& p, hipStream_t s) {
+    hipLaunchKernelGGL(PK_K1_KERNEL_XCHG_PACK, dim3(1), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+// move the listed payloads (x.cnt): pack = slot -> payload, else payload -> slot
+hipError_t pk_launch_xchg_move(const PkXchgArgs& x, bool pack, hipStream_t s) {
+    const uint64_t items = (uint64_t)x.items * ((x.pay16 + PK_XCHG_CHUNK - 1u) / PK_XCHG_CHUNK);
+    const u32 grid = items < 8192u ? (u32)items : 8192u;
+    if (!grid) return hipSuccess;   // no payload can move (max_payloads or n_payloads is 0)
+    if (pack) hipLaunchKernelGGL((pk_xchg_move_kernel<true>), dim3(grid), dim3(256), 0, s, x);
+    else hipLaunchKernelGGL((pk_xchg_move_kernel<false>), dim3(grid), dim3(256), 0, s, x);
     return hipGetLastError();
 }

@@ -255,4 +255,58 @@ struct PkArchArgs {
     uint32_t i_mask, s_mask;
     uint32_t n_cells, slot0;
     uint32_t env0, env1;
+    // archive exchange (pk_archive_exchange_enable), null without it: per cell what was already
+    // sent on and whether the record changed since the last delta pack.  An update only sets dirty.
+    uint32_t* x_sent_visits;     // [n_cells]
+    uint32_t* x_sent_picks;      // [n_cells]
+    uint32_t* x_dirty;           // [n_cells]
+    // pk_archive_merge runs the four update phases with records in the place of envs (the <true>
+    // instances): item i of [0, env1) is rec[i], tgt / flag / map are the merge's own arrays
+    const struct pk_xrec* rec;   // caller's records
+    uint32_t* s_vis;             // scratch entries: the visits and picks of the records from the
+    uint32_t* s_pick;            // key's first payload on (s_cnt counts those records)
+    uint32_t* x_cnt;             // the list of winners the payload mover runs over: count ...
+    uint32_t* x_cell;            // ... the winner's cell ...
+    uint32_t* x_pay;             // ... and its payload row
+    uint32_t n_payloads;         // rows of the caller's payload array
+    uint32_t format;             // this handle's pk_archive_format
+};
+
+// Archive exchange: a payload is one whole slot as linear bytes, the slot's parts in a fixed order
+// at 16-byte-aligned offsets (pk_capi.cpp xchg_args states the order).  A part is an array of the
+// handle with one fixed-size row per slot, so a mover's 16-byte piece q of a payload belongs to the
+// part p with off16[p] <= q < off16[p + 1] and sits at base[p] + slot * stride[p] + (q - off16[p]) * 16.
+// The trajectory part's origin and flag words are kept a word per slot: they travel as one piece
+// {origin, flags, 0, 0} built in registers (head16).
+#define PK_XCHG_MAX_PARTS 10u
+#define PK_XCHG_VERSION 1u       // payload layout version, the top byte of pk_archive_format
+#define PK_XCHG_MAX_RECORDS 65536u
+#define PK_XCHG_CHUNK 1024u      // 16-byte pieces of one payload a workgroup moves
+
+struct PkXchgArgs {
+    uint8_t* base[PK_XCHG_MAX_PARTS];
+    uint32_t stride[PK_XCHG_MAX_PARTS];   // bytes per slot of the part's array
+    uint32_t off16[PK_XCHG_MAX_PARTS + 1u];
+    uint32_t nparts;
+    uint32_t head16;             // the piece of {origin, flags, 0, 0}; PK_ARCH_NONE without trajectories
+    int32_t* bt_origin;          // [n_slots]
+    uint32_t* bt_flags;          // [n_slots]
+    uint8_t* b_filled;           // [n_slots] unpack marks the slot filled ...
+    uint8_t* b_ep_filled;        // ... with an episode part
+    uint8_t* payload;            // caller's rows of pay16 * 16 bytes
+    uint32_t pay16;
+    const uint32_t* cnt;         // device-built list: count, cell and payload row per item
+    const uint32_t* cell;
+    const uint32_t* pay;
+    uint32_t slot0;
+    uint32_t items;              // upper bound of listed items, sizes the grid
+};
+
+// pk_archive_pack: the one-workgroup scan that writes the records, numbers the payloads in cell
+// order and lists them
+struct PkPackArgs {
+    PkArchArgs a;
+    struct pk_xrec* out;         // caller's records [count]
+    uint32_t* n_payloads_out;    // caller's word, or null
+    uint32_t cell0, count, max_payloads, delta;
 };

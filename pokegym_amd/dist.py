@@ -2,8 +2,10 @@
 
 Envs are independent, so env.step has no data-path collective: rank g of W
 owns the contiguous env-id range shard_range(N, W, g) and runs it on its own GPU.  The only
-collective is the all-reduce (sum) of a few float64 episode statistics per logging interval —
-over RCCL/xGMI on MI355X (backend "nccl"), or gloo on CPU.
+collective on the step path is the all-reduce (sum) of a few float64 episode statistics per logging
+interval — over RCCL/xGMI on MI355X (backend "nccl"), or gloo on CPU.  Between steps, and only when
+the training loop asks for it, archive_all_gather exchanges what the ranks' exploration archives
+learned (VecEnv.archive_sync).
 """
 from __future__ import annotations
 
@@ -121,3 +123,18 @@ class InfoStats:
         ns = len(STATS_FIELDS)
         return {"info_records": n, "stats": dict(zip(STATS_FIELDS, mean[:ns])),
                 "reward": dict(zip(REWARD_FIELDS, mean[ns:]))}
+
+
+def archive_all_gather(records: torch.Tensor, payloads: torch.Tensor, rows: torch.Tensor, group=None):
+    """all_gather of one rank's packed archive cells (BatchedEmulator.archive_pack): the records, a
+    fixed number of payload rows and the per-record statistics rows, the same shapes on every rank.
+    Returns three lists with one tensor per rank, in rank order."""
+    world = dist.get_world_size(group)
+    out = []
+    for t in (records, payloads, rows):
+        t = t.contiguous()
+        bufs = [torch.empty_like(t) for _ in range(world)]
+        if t.numel():
+            dist.all_gather(bufs, t, group=group)
+        out.append(bufs)
+    return out

@@ -299,6 +299,71 @@ class BatchedEmulator:
         return {"used": int(used.value), "overflow": int(overflow.value), "keys": keys, "scores": scores,
                 "lengths": lengths, "visits": visits, "picks": picks}
 
+    # -- archive exchange (stream-ordered except enable) ----------------------------------
+    # a packed cell: pk_xrec, 48 bytes (include/pokegym_amd.h); records travel as uint8 (k, 48) tensors
+    XREC = np.dtype([("key", "<u8"), ("score", "<f8"), ("length", "<u4"), ("visits", "<u4"), ("picks", "<u4"),
+                     ("payload", "<i4"), ("format", "<u4"), ("reserved", "<u4", (3,))])
+
+    def archive_exchange_enable(self):
+        """Let the archive pack its cells and merge those of other handles (pk_archive_exchange_enable;
+        once, synchronous; needs archive_create)."""
+        check(self._L.pk_archive_exchange_enable(self._h), "pk_archive_exchange_enable")
+
+    @property
+    def archive_payload_bytes(self) -> int:
+        """Bytes of one payload (a whole slot), 0 before archive_exchange_enable."""
+        return int(self._L.pk_archive_payload_bytes(self._h))
+
+    @property
+    def archive_format(self) -> int:
+        """The payload layout this handle packs and accepts (pk_archive_format)."""
+        return int(self._L.pk_archive_format(self._h))
+
+    def archive_pack(self, delta: bool = False, cell0: int = 0, count: int | None = None, max_payloads: int | None = None):
+        """Cells [cell0, cell0 + count) as (records, payloads, n_payloads) device tensors
+        (pk_archive_pack, on the current stream): records uint8 (count, 48) — view them on the host
+        with BatchedEmulator.XREC — payloads uint8 (max_payloads, archive_payload_bytes) and
+        n_payloads an int32 scalar tensor, the rows written.  delta=False packs every cell in use
+        with its full counts and changes nothing; delta=True packs what this handle counted since
+        its last delta pack and ships only the cells whose record it replaced since (at most
+        max_payloads of them, the rest with the next delta pack).  max_payloads defaults to count."""
+        count = self.archive_cells - cell0 if count is None else int(count)
+        max_payloads = count if max_payloads is None else int(max_payloads)
+        records = torch.zeros((max(count, 1), self.XREC.itemsize), dtype=torch.uint8, device=self.device)
+        payloads = torch.zeros((max_payloads, max(self.archive_payload_bytes, 16)), dtype=torch.uint8, device=self.device)
+        n_payloads = torch.zeros((), dtype=torch.int32, device=self.device)
+        check(self._L.pk_archive_pack(self._h, _native.PK_XCHG_DELTA if delta else 0, int(cell0), count, max_payloads,
+                                      ctypes.c_void_p(records.data_ptr()),
+                                      ctypes.c_void_p(payloads.data_ptr()) if max_payloads else None,
+                                      ctypes.c_void_p(n_payloads.data_ptr()), self._stream()), "pk_archive_pack")
+        return records[:count], payloads, n_payloads
+
+    def archive_merge(self, records: torch.Tensor, payloads: torch.Tensor | None, out: torch.Tensor | None = None):
+        """Merge packed cells into this archive (pk_archive_merge, on the current stream): records
+        uint8 (k, 48), payloads uint8 (m, archive_payload_bytes) or None, both on this device; the
+        winners' payloads are written into their cells' slots.  Returns out, int32 (k,): the cell
+        each record won, -1 else."""
+        if records.dtype != torch.uint8 or records.device != self.device or records.dim() != 2 \
+                or records.shape[1] != self.XREC.itemsize or not records.is_contiguous():
+            raise ValueError("records must be a contiguous uint8 (k, 48) tensor on the emulator's device")
+        k = int(records.shape[0])
+        m = 0
+        if payloads is not None:
+            m = int(payloads.shape[0])
+            if payloads.dtype != torch.uint8 or payloads.device != self.device or not payloads.is_contiguous() \
+                    or (m and payloads.shape[1] != self.archive_payload_bytes):
+                raise ValueError("payloads must be a contiguous uint8 (m, archive_payload_bytes) tensor on the device")
+        if out is None:
+            out = torch.full((k,), -1, dtype=torch.int32, device=self.device)
+        elif out.dtype != torch.int32 or out.device != self.device or out.numel() != k or not out.is_contiguous():
+            raise ValueError("out must be a contiguous int32 tensor of one element per record on the device")
+        if k == 0:
+            return out
+        check(self._L.pk_archive_merge(self._h, ctypes.c_void_p(records.data_ptr()), k,
+                                       ctypes.c_void_p(payloads.data_ptr()) if m else None, m,
+                                       ctypes.c_void_p(out.data_ptr()), self._stream()), "pk_archive_merge")
+        return out
+
     # -- action trajectories (stream-ordered except enable) -------------------------------
     def traj_enable(self):
         """Record every env's actions from here on (pk_traj_enable; once, synchronous).  Call it

@@ -246,7 +246,7 @@ class VecEnv:
                  heatmap: bool = False, reward: bool = True, power_on: bool = False, batch_size: int | None = None,
                  state_pool=None, pool_seed: int = 0, bank_slots: int = 0, bank_episodes: bool = False,
                  fork_slots: int = 0, archive_cells: int = 0, archive_seed: int = 0, archive_shift: int = 0,
-                 record_trajectories: bool = False):
+                 record_trajectories: bool = False, archive_exchange: bool = False):
         """reward=False: the screen-obs env of configs[3] — obs is the (144, 160) u8 screen, rewards are
         0 and episodes end at max_episode_steps.  power_on=True starts (and resets) every env from
         the cartridge's power-on state instead of a savestate.
@@ -271,7 +271,10 @@ class VecEnv:
         archive_explore(mask) resumes envs from cells drawn by visit count with archive_seed;
         archive_shift is cell_keys()'s coordinate shift.  Both are calls of the training loop between
         steps: the auto-reset path does not explore, and the archive is not driven per sub-batch
-        on the sub-batch streams.
+        on the sub-batch streams.  archive_exchange=True (needs archive_cells) lets the archive leave
+        the handle: archive_export() / archive_import() move its cells — records, whole slots and this
+        class's per-slot episode return / length / start slot — as host arrays, and archive_sync()
+        exchanges what the archives of a torch.distributed group learned since the last call.
 
         record_trajectories=True records every env's actions since its last reset on the device
         (pk_traj_enable): trajectory(env), and with bank_episodes slot_trajectory(slot) and
@@ -353,8 +356,11 @@ class VecEnv:
         self.archive_cells, self.archive_shift = int(archive_cells), int(archive_shift)
         self._arch0 = 0             # first slot of the archive's cells
         self._arch_out = None
+        self.archive_exchange = bool(archive_exchange)
         if self.archive_cells and not bank_episodes:
             raise ValueError("archive_cells needs bank_episodes=True")
+        if self.archive_exchange and not self.archive_cells:
+            raise ValueError("archive_exchange needs archive_cells")
         if state_pool is not None or bank_slots or self.fork_slots or self.archive_cells:
             pool = [st if isinstance(st, (bytes, bytearray)) else _read(st) for st in (state_pool or [])]
             if state_pool is not None and not pool:
@@ -384,6 +390,8 @@ class VecEnv:
                 if self.archive_cells:
                     self.emu.archive_create(self._arch0, self.archive_cells, archive_seed)
                     self._arch_out = torch.full((n_phys,), -1, dtype=torch.int32, device=self.device)
+                    if self.archive_exchange:
+                        self.emu.archive_exchange_enable()
         elif bank_episodes:
             raise ValueError("bank_episodes=True needs a bank: state_pool, bank_slots or fork_slots")
 
@@ -581,6 +589,82 @@ class VecEnv:
             else:
                 self._slots.copy_(new)
         return drawn.to(torch.int32)
+
+    def _exchange(self):
+        if not self.archive_exchange:
+            raise RuntimeError("VecEnv(archive_cells=..., archive_exchange=True) exchanges archive cells")
+        self._join_streams()
+
+    def _cell_rows(self) -> torch.Tensor:
+        """What this class keeps per slot, for the cells' slots: float64 (archive_cells, 4) rows of
+        _ck_return, _ck_length, _ck_valid, _ck_slots — row c travels with record c of a pack."""
+        sl = slice(self._arch0, self._arch0 + self.archive_cells)
+        return torch.stack([self._ck_return[sl], self._ck_length[sl], self._ck_valid[sl].to(torch.float64),
+                            self._ck_slots[sl].to(torch.float64)], dim=1)
+
+    def _place_rows(self, cell_out: torch.Tensor, rows: torch.Tensor):
+        """Row i goes to the slot of cell cell_out[i]; the rows of records that won nothing go nowhere."""
+        last = self._ck_return.numel() - 1
+        won = cell_out.long()
+        slots = torch.where(won >= 0, won + self._arch0, last)
+        self._ck_return[slots] = rows[:, 0]
+        self._ck_length[slots] = rows[:, 1]
+        self._ck_valid[slots] = rows[:, 2] != 0
+        self._ck_valid[last] = False
+        self._ck_slots[slots] = rows[:, 3].to(torch.int32)
+
+    def archive_export(self) -> dict:
+        """The whole archive as host arrays (a full pack, which changes nothing; synchronises):
+        "records" uint8 (archive_cells, 48) in cell order, "payloads" uint8 (cells in use,
+        emu.archive_payload_bytes), and this class's rows "ck_return", "ck_length", "ck_valid",
+        "ck_slots" per cell.  np.savez(path, **d) keeps it across a restart."""
+        self._exchange()
+        records, payloads, n = self.emu.archive_pack()
+        rows = self._cell_rows().cpu().numpy()
+        return {"records": records.cpu().numpy(), "payloads": payloads[:int(n)].cpu().numpy(),
+                "ck_return": rows[:, 0].copy(), "ck_length": rows[:, 1].copy(), "ck_valid": rows[:, 2] != 0,
+                "ck_slots": rows[:, 3].astype(np.int32)}
+
+    def archive_import(self, d) -> torch.Tensor:
+        """Merge an archive_export() dict (of this or another VecEnv with the same geometry) into the
+        archive (emu.archive_merge): a cell takes an imported record when it is new or strictly
+        better, with its slot and its episode return / length / start slot.  Start slots name the
+        exporter's state pool: use the same pool.  Returns the cell each record won (int32, -1 else)."""
+        self._exchange()
+        dev = self.device
+        records = torch.from_numpy(np.ascontiguousarray(d["records"], np.uint8)).to(dev)
+        payloads = torch.from_numpy(np.ascontiguousarray(d["payloads"], np.uint8)).to(dev)
+        rows = torch.from_numpy(np.stack([np.asarray(d["ck_return"], np.float64), np.asarray(d["ck_length"], np.float64),
+                                          np.asarray(d["ck_valid"], np.float64), np.asarray(d["ck_slots"], np.float64)],
+                                         axis=1)).to(dev)
+        if rows.shape[0] != records.shape[0]:
+            raise ValueError("archive_import: one statistics row per record")
+        out = self.emu.archive_merge(records, payloads)
+        self._place_rows(out, rows)
+        return out
+
+    def archive_sync(self, group=None, max_payloads: int | None = None):
+        """Exchange with the other ranks of a torch.distributed group what the archives learned since
+        the last call: a delta pack (this rank's own new visits and picks, and at most max_payloads
+        of the cells whose record it replaced; default: all cells — the rest goes with the next
+        call), an all_gather of records, payload rows and statistics rows, then a merge of every
+        other rank's buffers in ascending rank order.  Counts that came from other ranks are never
+        sent on.  A collective: every rank calls it, with the same max_payloads.  World size 1 (or no
+        process group) is a no-op.  On the current stream after a pipeline join."""
+        import torch.distributed as dist
+        from .dist import archive_all_gather
+        if not self.archive_exchange:
+            raise RuntimeError("VecEnv(archive_cells=..., archive_exchange=True) exchanges archive cells")
+        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+            return
+        self._join_streams()
+        max_payloads = self.archive_cells if max_payloads is None else int(max_payloads)
+        records, payloads, _ = self.emu.archive_pack(delta=True, max_payloads=max_payloads)
+        recs, pays, rows = archive_all_gather(records, payloads, self._cell_rows(), group)
+        me = dist.get_rank(group)
+        for r in range(len(recs)):
+            if r != me:
+                self._place_rows(self.emu.archive_merge(recs[r], pays[r]), rows[r])
 
     def archive_state(self) -> dict:
         """The archive as host arrays (emu.archive_read; synchronous)."""
