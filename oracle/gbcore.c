@@ -935,12 +935,14 @@ int gb_render_from_state(const uint8_t* state, uint32_t len, uint8_t* out) {
     const uint8_t* r = state + 8375;
     gb->LCDC = r[0]; gb->BGP = r[1]; gb->OBP0 = r[2]; gb->OBP1 = r[3];
     gb->ly_window = -1;
-    /* render each line with the latched per-line params (SCX,SCY,WX,WY) */
+    /* render each line with the latched per-line params (SCX,SCY,WX,WY,tile-data select): the
+     * line's LCDC.4 is the latched byte, as pk_load_env builds it */
     for (int y = 0; y < GB_ROWS; y++) {
         gb->SCX = state[8405 + y * 5 + 0];
         gb->SCY = state[8405 + y * 5 + 1];
         gb->WX = state[8405 + y * 5 + 2];
         gb->WY = state[8405 + y * 5 + 3];
+        gb->LCDC = (uint8_t)((r[0] & ~0x10) | ((state[8405 + y * 5 + 4] & 1) << 4));
         render_scanline(gb, y);
     }
     memcpy(out, gb->screen, GB_ROWS * GB_COLS);

@@ -534,3 +534,71 @@ def lcd_toggle_rom() -> bytes:
          ".toff:", "xor a", "ldh [$07], a", "jp main",
          "timer_isr:", "push af", "ld a, [$c010]", "inc a", "ld [$c010], a", "pop af", "reti"]
     return build_rom("\n".join(L), n_banks=2, title="LCDTOGGLE")
+
+
+def raster_fx_rom() -> bytes:
+    """Per-line register changes — what K1's line latch must get right: a line's LCDC, scroll,
+    window position, palettes and window line counter are latched at its mode-0 event (pk_step.hip,
+    the per-event latch) or, for a CPU halted until VBlank, in bulk by the HALT skip-ahead.  A STAT
+    LY=LYC handler rewrites SCX, SCY, WX, WY, BGP, OBP0, OBP1 and LCDC bits 0-6 (LCD kept on) from
+    an LFSR the main loop mixes the joypad and a pass counter into, then moves LYC 9..24 lines down
+    (eight or so rewrites a frame, on lines that differ from env to env): window enable off for a
+    band and on again, 8x8 <-> 8x16 objects mid-frame, BG enable, both map selects, the tile-data
+    select, WX on and off screen, WY crossing the line.  OAM holds 40 overlapping objects with every
+    attribute, fourteen of them on the same lines.  The main loop waits for a pass-dependent line;
+    every fourth pass then switches the STAT interrupt off and HALTs until VBlank (the skip-ahead's
+    bulk latch carries the handler's last LCDC, palettes and a non-zero window counter), the others
+    write OBP0 and go on without HALT.  Set-up (all tile data, both maps, OAM) runs with the LCD off
+    in under three frames."""
+    L = ["wSeed equ $c0f0", "wPass equ $c0f1", "wVbl equ $c0f2",
+         "section 0", "org $0040", "jp h_vbl", "org $0048", "jp h_stat", "org $0050", "reti", "org $0058", "reti",
+         "org $0060", "reti", "org $0100", "nop", "jp start", "org $0150",
+         "start:", "di", "ld sp, $dff0", "xor a", "ldh [$40], a", "ldh [$0f], a",
+         # tile data 8000-97FF and both maps, four bytes a pass (19 cycles a byte: LCD off < 3 frames)
+         "ld hl, $8000", "ld b, $a7", "ld c, $3d",
+         ".f:", "ld a, l", "xor b", "ld [hl+], a", "add a, c", "ld [hl+], a", "rrca", "ld b, a", "ld [hl+], a", "xor l", "ld [hl+], a",
+         "ld a, h", "cp $a0", "jr nz, .f",
+         # OAM: objects 0-13 on the same lines (Y 60..63), the rest 5 lines apart; X 4 apart (they
+         # overlap, the first is clipped at the left edge), tile 3 n + 1, attribute bits 4-7 varied
+         "ld hl, $fe00", "ld b, 0",
+         ".o:", "ld a, b", "cp 14", "jr nc, .o2", "and $03", "add a, 60", "jr .oy",
+         ".o2:", "sub 14", "ld c, a", "add a, a", "add a, a", "add a, c", "add a, 16",
+         ".oy:", "ld [hl+], a",
+         "ld a, b", "add a, a", "add a, a", "add a, 4", "ld [hl+], a",
+         "ld a, b", "add a, a", "add a, b", "inc a", "ld [hl+], a",
+         "ld a, b", "swap a", "ld c, a", "add a, a", "add a, c", "and $f0", "ld [hl+], a",
+         "inc b", "ld a, b", "cp 40", "jr nz, .o",
+         "ld a, $5a", "ld [wSeed], a", "xor a", "ld [wPass], a",
+         "ld a, 40", "ldh [$4a], a", "ld a, 47", "ldh [$4b], a", "ld a, $e4", "ldh [$47], a", "ld a, $d2", "ldh [$48], a",
+         "ld a, $39", "ldh [$49], a", "ld a, 12", "ldh [$45], a", "ld a, $40", "ldh [$41], a",
+         "ld a, $03", "ldh [$ff], a", "ld a, $f3", "ldh [$40], a", "ei",
+         "main:",
+         "ld a, $10", "ldh [$00], a", "ldh a, [$00]", "ldh a, [$00]", "and $0f", "ld e, a",
+         "ld a, [wPass]", "inc a", "ld [wPass], a", "ld b, a",
+         "ld a, [wSeed]", "xor e", "add a, b", "jr nz, .s", "ld a, $5a", ".s:", "ld [wSeed], a",
+         # the pass's line T = 8 + (seed & $7f), at most 135: wait for a line above it, then for T
+         "and $7f", "add a, 8", "ld d, a",
+         ".w1:", "ldh a, [$44]", "cp d", "jr nc, .w1",
+         ".w2:", "ldh a, [$44]", "cp d", "jr c, .w2",
+         "ld a, b", "and $03", "jr z, .halt",
+         "ld a, [wSeed]", "xor b", "ldh [$48], a", "jp main",
+         # HALT until VBlank with nothing else to wake the CPU: STAT interrupt off, IF clear
+         ".halt:", "di", "xor a", "ldh [$41], a", "ldh [$0f], a", "ld a, $01", "ldh [$ff], a", "ei", "halt", "nop",
+         "di", "ld a, $40", "ldh [$41], a", "ld a, $03", "ldh [$ff], a", "ei", "jp main",
+         "h_vbl:", "push af", "ld a, [wVbl]", "inc a", "ld [wVbl], a", "pop af", "reti",
+         "h_stat:", "push af", "push bc", "push hl",
+         "ld hl, wSeed", "ld a, [hl]", "ld b, a", "add a, a", "jr nc, .n", "xor $1d", ".n:", "and a", "jr nz, .z", "ld a, $5a",
+         ".z:", "ld [hl], a", "ld c, a",
+         "ldh [$43], a",                                                     # SCX
+         "rlca", "rlca", "rlca", "xor b", "ldh [$42], a",                    # SCY
+         "ld a, b", "and $bf", "ldh [$4b], a",                               # WX 0..63, 128..191
+         "ld a, c", "and $3f", "ldh [$4a], a",                               # WY 0..63
+         "ld a, b", "xor $e4", "ldh [$47], a",                               # BGP
+         "ld a, c", "xor $d2", "ldh [$48], a",                               # OBP0
+         "ld a, b", "add a, c", "ldh [$49], a",                              # OBP1
+         "ld a, b", "rrca", "xor c", "or $80", "ldh [$40], a",               # LCDC bits 0-6, LCD on
+         # LYC 9..24 lines down; past line 143: 1..8 of the next frame
+         "ld a, c", "and $0f", "add a, 9", "ld c, a", "ldh a, [$45]", "add a, c", "cp 144", "jr c, .l",
+         "ld a, b", "and $07", "inc a", ".l:", "ldh [$45], a",
+         "pop hl", "pop bc", "pop af", "reti"]
+    return build_rom("\n".join(L), n_banks=2, title="RASTERFX")

@@ -187,7 +187,8 @@ def frame_case(name: str, n: int, frames: int | None = None):
         return game_rom(), state, acts if frames is None else acts[:frames], True
     rom, default, seed = {"pkbench": (game_rom, 240, 40), "fuzz3": (lambda: fuzz.fuzz_rom(3), 100, 41),
                           "dma_wait": (fuzz.dma_wait_rom, 100, 42),
-                          "vram_midframe": (fuzz.vram_midframe_rom, 100, 43)}[name]
+                          "vram_midframe": (fuzz.vram_midframe_rom, 100, 43),
+                          "raster_fx": (fuzz.raster_fx_rom, 100, 44)}[name]
     acts = np.random.default_rng(seed).integers(0, 9, size=(frames or default, n), dtype=np.uint8)
     return rom(), None, acts, name != "fuzz3"
 
@@ -232,7 +233,7 @@ def test_check_frame_end_sees_each_violation():
 
 
 # ------------------------------------------------------------------ oracle and host-sim K1 ------
-CASES = ["pkbench", "warp", "fuzz3", "dma_wait", "vram_midframe"]
+CASES = ["pkbench", "warp", "fuzz3", "dma_wait", "vram_midframe", "raster_fx"]
 
 
 @functools.lru_cache(maxsize=None)

@@ -279,6 +279,37 @@ def test_vram_midframe_parity(small, monkeypatch):
     assert all(np.array_equal(scr[e], grey[ref_scr[e]]) for e in range(n))
 
 
+@pytest.mark.parametrize("small", [False, True])
+def test_raster_fx_parity(small, monkeypatch):
+    """Registers rewritten line by line (fuzz.py raster_fx_rom): a STAT LY=LYC handler changes SCX,
+    SCY, WX, WY, the three palettes and LCDC bits 0-6 on env-dependent lines, 40 overlapping objects
+    (fourteen on the same lines) switch between 8x8 and 8x16 mid-frame, and every fourth pass HALTs
+    until VBlank partway down the frame — K1's per-event line latch and the bulk latch of the HALT
+    skip-ahead, with the window line counter they carry; 24/8 steps, whole state and screen vs the
+    oracle, in the default kernel and in the small-LDS kernel."""
+    from pokegym_amd.testrom.fuzz import raster_fx_rom
+    if small:
+        monkeypatch.setenv("PK_K1_SMALL", "1")
+        monkeypatch.setenv("PK_WAVE_LANES", "32")
+        monkeypatch.setenv("PK_K1_BLOCK", "256")
+    import torch
+    from pokegym_amd.emulator import BatchedEmulator
+    rom, n, steps = raster_fx_rom(), 256, 6
+    actions = np.random.default_rng(29).integers(0, 9, size=(steps, n), dtype=np.uint8)
+    emu = BatchedEmulator(rom, n, render=True)
+    for t in range(steps):
+        emu.step(torch.from_numpy(actions[t]).to(emu.device))
+    torch.cuda.synchronize()
+    gpu = [emu.snapshot(e) for e in range(n)]
+    scr = emu.screen.cpu().numpy()
+    emu.close()
+    ref, ref_scr = oracle.batch_run(rom, None, actions)
+    grey = np.array([0xFF, 0x99, 0x55, 0x00], np.uint8)
+    bad = [(e, _diff(gpu[e], ref[e].tobytes())) for e in range(n) if gpu[e] != ref[e].tobytes()]
+    assert not bad, bad[:4]
+    assert all(np.array_equal(scr[e], grey[ref_scr[e]]) for e in range(n))
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("small", [False, True])
 def test_dma_wait_parity(small, monkeypatch):
@@ -426,8 +457,9 @@ def _lockstep(rom, state, acts, frame_skip, release_frame, tally=None):
 # lines inside K1, lane by lane), the warp fixture 1.6 s at 144 and fuzz3 1.6 s at 72.  vram_midframe
 # cannot be halved again: its 3 LCD-off boot frames would be more than 10 % of 18.  The warp
 # fixture's first 72 frames hold the recorded door warp (LCD off in frames 57-61) and ten rendered
-# frames after it.
-PER_FRAME_STEPS = {"pkbench": 72, "fuzz3": 36, "vram_midframe": 36, "warp": 72}
+# frames after it.  raster_fx took 0.6 s at 36 frames (its register rewrites flush nothing: no VRAM
+# or OAM write); its 2 LCD-off boot frames keep it from being halved below 36 as well.
+PER_FRAME_STEPS = {"pkbench": 72, "fuzz3": 36, "vram_midframe": 36, "warp": 72, "raster_fx": 36}
 _per_frame_tallies = {}
 
 
@@ -443,11 +475,12 @@ def _per_frame(name, small):
 
 
 @pytest.mark.parametrize("small", [False, True])
-@pytest.mark.parametrize("name", ["pkbench", "fuzz3", "vram_midframe", "warp"])
+@pytest.mark.parametrize("name", ["pkbench", "fuzz3", "vram_midframe", "warp", "raster_fx"])
 def test_per_frame_parity(name, small, monkeypatch):
     """frame_skip=1, release_frame=8: every frame is a step end and is rasterised (K1 enters with
     s.render set; the pend_hit / flush_lines filter and K2 run on every frame).  96 envs — one full
-    64-env group and a ragged half — of pkbench, fuzz_rom(3), vram_midframe_rom and the warp fixture
+    64-env group and a ragged half — of pkbench, fuzz_rom(3), vram_midframe_rom, raster_fx_rom (its
+    per-line LCDC / scroll / window / palette rewrites and mid-frame HALTs) and the warp fixture
     (test_map_load_warp_parity's action layout with each action held 24 frames, so the LCD-off
     frames of the map load are rendered and compared), PER_FRAME_STEPS frames; whole v9 state and
     screen vs the oracle after every frame, in the default kernel and in the small-LDS kernel; every
