@@ -37,6 +37,8 @@
  *                    episode, recorded per env and carried through checkpoints, resumes and the archive
  *   pk_archive_pack / pk_archive_merge   no reference equivalent: an archive's cells as records and
  *                    whole-slot payloads, and their merge into the archive of another handle
+ *   pk_frame_keys    no reference equivalent: Go-Explore's cell of a frame, the screen downscaled to a
+ *                    few blocks and quantised to a few levels, as a 64-bit key for the archive
  * With PK_F_REWARD, pk_step also runs the reward stack of Environment.step
  * (environment.py:1338-1612) and pk_reset follows Environment.reset (:1233-1334).
  */
@@ -49,7 +51,7 @@
 extern "C" {
 #endif
 
-#define PK_ABI_VERSION 11
+#define PK_ABI_VERSION 12
 #define PK_STATE_V9_BYTES 142610u
 #define PK_SCREEN_ROWS 144u
 #define PK_SCREEN_COLS 160u
@@ -281,7 +283,8 @@ int pk_bank_rejects(pk_handle* h, uint64_t* out);
  * handle without one fails with a negative code and does nothing.  Memory: 76 to 100 bytes per cell,
  * and per env of the handle 81 to 153 bytes of per-call words (the tables are powers of two).
  *
- * pk_cell_keys (any handle; no archive, no PK_F_REWARD needed): for each env of the range
+ * pk_cell_keys (any handle; no archive, no PK_F_REWARD needed; meaningful on Pokémon Red's WRAM
+ * layout, pk_frame_keys below is the key of any cartridge): for each env of the range
  *   keys[e] = map | (x >> shift) << 8 | (y >> shift) << 16 | badges << 24
  * with map = guest 0xD35E, x = 0xD362, y = 0xD361, badges = 0xD356; shift in 0..7.  keys_dev is a
  * full-size device u64[n]; only [env0, env0 + count) is written.
@@ -334,6 +337,41 @@ int pk_archive_explore(pk_handle* h, const uint8_t* mask_dev, uint32_t env0, uin
                        int32_t* slot_of_env_out_dev, void* stream);
 int pk_archive_read(pk_handle* h, uint32_t* used, uint64_t* keys, double* scores, uint32_t* lengths,
                     uint32_t* visits, uint32_t* picks, uint64_t* overflow);
+
+/* Frame cells: Go-Explore's own cell, the frame downscaled and quantised, for any cartridge.  The
+ * screen is cut into blocks of bw x bh pixels, bw a multiple of 8 that divides 160 (8, 16, 32, 40, 80,
+ * 160) and bh one that divides 144 (8, 16, 24, 48, 72, 144); pk_frame_cells(bw, bh) is the number of
+ * blocks C = (160 / bw) * (144 / bh), 0 for any other pair.  levels is in 2..256.
+ *
+ * pk_frame_keys, for each env e of the range, with mix splitmix64's finaliser (pk_archive_explore
+ * above), G = 0x9E3779B97F4A7C15 and all sums mod 2^64:
+ *   v(y, x) = screen[e][y][x] >> 6          0..3: 0xFF / 0x99 / 0x55 / 0x00 -> 3 / 2 / 1 / 0; any byte is legal
+ *   block i = by * (160 / bw) + bx (row-major),  S_i = the sum of v over the block's bw * bh pixels
+ *   q_i     = (S_i * levels) div (3 * bw * bh + 1)                          integers; 0..levels - 1
+ *   sum     = the sum over i of mix(G * (i + 1) + q_i), plus mix(salt[e]) with a salt
+ *   key     = mix(sum); UINT64_MAX becomes UINT64_MAX - 1 (the archive reserves UINT64_MAX)
+ *             with a salt and salt[e] == UINT64_MAX: key = UINT64_MAX ("no cell" passes through)
+ *   keys_dev[e] = key,  cells_dev[e][i] = q_i
+ * The terms are added, not chained, so the result does not depend on the order of the reduction: it
+ * is the same from run to run.
+ *   screen_dev  NULL = the handle's own screen (pk_screen_ptr; needs PK_F_RENDER, the call fails
+ *               without it), which every step rewrites and every reset, load, resume and merge
+ *               restores; or a caller's device u8[n][144][160], 16-byte aligned, on any handle.
+ *   salt_dev    NULL, or a full-size device u64[n], e.g. pk_cell_keys' output for a key of frame and
+ *               RAM together (mix(0) = 0: a salt of 0 is the one salt that leaves the key as it is).
+ *               It may be keys_dev itself: each env reads its word before writing it.
+ *   keys_dev    required, full-size device u64[n].
+ *   cells_dev   NULL, or a device u8[n][C]: the cell image, a small global observation.
+ * Only the elements and rows of [env0, env0 + count) are written; the range follows pk_step_range's
+ * rule, as pk_cell_keys' does.  One launch, stream-ordered, no host sync, no allocation; the archive
+ * is not touched, so calls over disjoint ranges may run concurrently.  A failed call (bad bw, bh or
+ * levels, NULL keys_dev, a misaligned screen_dev, a range past n) returns a negative code, sets
+ * pk_last_error and writes nothing.  A handle that never calls it makes exactly the launches and
+ * allocations it made before. */
+uint32_t pk_frame_cells(uint32_t bw, uint32_t bh);
+int pk_frame_keys(pk_handle* h, uint32_t bw, uint32_t bh, uint32_t levels, const uint8_t* screen_dev,
+                  const uint64_t* salt_dev, uint64_t* keys_dev, uint8_t* cells_dev, uint32_t env0, uint32_t count,
+                  void* stream);
 
 /* Action trajectories: how an env got where it is.  After pk_traj_enable every env has
  *   actions  u8[capacity]  the action of every step since the env's last reset, one byte per step

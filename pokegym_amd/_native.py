@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # PK_LIB selects an alternative in-tree build (A/B kernel experiments); default: lib/libpokegym_amd.so
 LIB_PATH = os.environ.get("PK_LIB") or os.path.join(HERE, "lib", "libpokegym_amd.so")
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 PK_F_RENDER = 1
 PK_F_REWARD = 2
 PK_F_RELOAD_ON_RESET = 4
@@ -43,7 +43,8 @@ EXPORTS = ("pk_create", "pk_destroy", "pk_last_error", "pk_abi_version", "pk_res
            "pk_archive_read",
            "pk_traj_enable", "pk_traj_capacity", "pk_traj_get", "pk_bank_traj_get",
            "pk_archive_exchange_enable", "pk_archive_payload_bytes", "pk_archive_format", "pk_archive_pack",
-           "pk_archive_merge")
+           "pk_archive_merge",
+           "pk_frame_cells", "pk_frame_keys")
 
 
 class PkConfig(ctypes.Structure):
@@ -129,6 +130,7 @@ def bind(L):
     bind_v9(L)
     bind_v10(L)
     bind_v11(L)
+    bind_v12(L)
 
 
 def bind_v2(L):
@@ -217,6 +219,15 @@ def bind_v11(L):
     L.pk_archive_format.restype = u32
     L.pk_archive_pack.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp, vp]
     L.pk_archive_merge.argtypes = [vp, vp, u32, vp, u32, vp, vp]
+
+
+def bind_v12(L):
+    """argtypes of the frame cells (ABI v12; shared with the host-simulation test build)."""
+    vp = ctypes.c_void_p
+    u32 = ctypes.c_uint32
+    L.pk_frame_cells.argtypes = [u32, u32]
+    L.pk_frame_cells.restype = u32
+    L.pk_frame_keys.argtypes = [vp, u32, u32, u32, vp, vp, vp, vp, u32, u32, vp]
 
 
 def check(rc: int, what: str):

@@ -50,6 +50,7 @@ hipError_t pk_launch_xchg_move(const PkXchgArgs& x, bool pack, hipStream_t s);
 hipError_t pk_launch_arch_out(const PkArchArgs& a, hipStream_t s);
 hipError_t pk_launch_cell_keys(const uint8_t* mem, uint32_t sh, uint32_t shift, uint64_t* keys, uint32_t env0,
                                uint32_t env1, hipStream_t s);
+hipError_t pk_launch_frame_keys(const PkCellArgs& a, hipStream_t s);
 hipError_t pk_launch_traj_record(const PkTrajArgs& a, hipStream_t s);
 hipError_t pk_launch_traj_reset(const PkTrajArgs& a, hipStream_t s);
 hipError_t pk_launch_traj_mark(const PkTrajArgs& a, hipStream_t s);
@@ -1612,6 +1613,30 @@ int pk_cell_keys(pk_handle* h, uint32_t shift, uint64_t* keys, uint32_t env0, ui
     if (shift > 7) return fail(-EINVAL, "shift must be 0..7");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(pk_launch_cell_keys(h->mem, h->ilv_sh, shift, keys, env0, env0 + count, (hipStream_t)stream));
+    return 0;
+}
+
+uint32_t pk_frame_cells(uint32_t bw, uint32_t bh) {
+    if (!bw || !bh || bw % 8u || bh % 8u || PK_COLS % bw || PK_ROWS % bh) return 0;
+    return (PK_COLS / bw) * (PK_ROWS / bh);
+}
+
+int pk_frame_keys(pk_handle* h, uint32_t bw, uint32_t bh, uint32_t levels, const uint8_t* screen, const uint64_t* salt,
+                  uint64_t* keys, uint8_t* cells, uint32_t env0, uint32_t count, void* stream) {
+    int rc;
+    if ((rc = check_range(h, env0, count))) return rc;
+    if (!pk_frame_cells(bw, bh))
+        return fail(-EINVAL, "blocks of %u x %u: bw must be a multiple of 8 that divides 160, bh one that divides 144", bw, bh);
+    if (levels < 2 || levels > 256) return fail(-EINVAL, "levels must be 2..256");
+    if (!keys) return fail(-EINVAL, "keys_dev is required");
+    if (!screen && !(h->flags & PK_F_RENDER))
+        return fail(-ENOTSUP, "the handle renders no screen (PK_F_RENDER): pass screen_dev");
+    if ((uintptr_t)screen % 16u) return fail(-EINVAL, "screen_dev must be 16-byte aligned");
+    HIPCHK(hipSetDevice(h->device));
+    PkCellArgs a;
+    a.screen = screen ? screen : h->screen; a.salt = salt; a.keys = keys; a.cells = cells;
+    a.env0 = env0; a.env1 = env0 + count; a.bw = bw; a.bh = bh; a.levels = levels;
+    HIPCHK(pk_launch_frame_keys(a, (hipStream_t)stream));
     return 0;
 }
 

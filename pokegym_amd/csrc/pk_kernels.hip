@@ -841,6 +841,83 @@ hipError_t pk_launch_cell_keys(const u8* mem, u32 sh, u32 shift, u64* keys, u32 
     return hipGetLastError();
 }
 
+// pk_frame_keys, workgroup = env: the screen downscaled to blocks of bw x bh pixels, each quantised to
+// `levels` levels, and the 64-bit key of that cell image (include/pokegym_amd.h states the model).
+// The screen is read once: lane l of pass k loads 16-byte piece PK_CELLS_WG * k + l, eight passes in
+// flight, and leaves the pixel sums of the piece's two halves (8 pixels each, <= 24) as two bytes in
+// LDS.  Behind one barrier, thread i adds the half sums of block i, quantises, writes the cell and
+// forms the block's 64-bit term.  The terms are added through LDS in two steps, not by shuffles: the
+// host-simulation build's wave is one lane.  A workgroup is one wave, so its barriers cost nothing
+// and a CU holds as many screens in flight as it holds waves.
+#ifndef PK_CELLS_WG
+#define PK_CELLS_WG 64u
+#endif
+#define PK_CELLS_PASSES ((PK_CELL_PIECES + PK_CELLS_WG - 1u) / PK_CELLS_WG)
+#define PK_K1_KERNEL_FRAME_KEYS pk_frame_keys_kernel
+__global__ void __launch_bounds__(PK_CELLS_WG) pk_frame_keys_kernel(PkCellArgs A) {
+    __shared__ uint16_t half[PK_CELL_PIECES];   // piece p: left half sum | right half sum << 8
+    __shared__ u64 red[PK_CELLS_WG];
+    const u32 tid = threadIdx.x, e = A.env0 + blockIdx.x;
+    const uint4* src = reinterpret_cast<const uint4*>(A.screen + (size_t)e * PK_SCREEN);
+#pragma unroll
+    for (u32 k0 = 0; k0 < PK_CELLS_PASSES; k0 += 8u) {
+        uint4 w[8];
+#pragma unroll
+        for (u32 j = 0; j < 8u; j++) {
+            const u32 p = (k0 + j) * PK_CELLS_WG + tid;
+            if (k0 + j < PK_CELLS_PASSES && p < PK_CELL_PIECES) w[j] = src[p];
+        }
+#pragma unroll
+        for (u32 j = 0; j < 8u; j++) {
+            const u32 p = (k0 + j) * PK_CELLS_WG + tid;
+            if (k0 + j >= PK_CELLS_PASSES || p >= PK_CELL_PIECES) continue;
+            // v = byte >> 6 per pixel; two dwords added bytewise (<= 6 a byte), then the four bytes summed
+            const u32 lo = ((w[j].x >> 6) & 0x03030303u) + ((w[j].y >> 6) & 0x03030303u);
+            const u32 hi = ((w[j].z >> 6) & 0x03030303u) + ((w[j].w >> 6) & 0x03030303u);
+            half[p] = (uint16_t)(((lo * 0x01010101u) >> 24) | ((hi * 0x01010101u) >> 24) << 8);
+        }
+    }
+    __syncthreads();
+    // half sum h = 20 y + x / 8 is byte h of the array: a block is tw of them in each of its bh rows
+    const u8* hb = reinterpret_cast<const u8*>(half);
+    const u32 nbx = PK_COLS / A.bw, tw = A.bw / 8u, nblk = nbx * (PK_ROWS / A.bh);
+    const u32 div = 3u * A.bw * A.bh + 1u;
+    u64 acc = 0;
+    for (u32 i = tid; i < nblk; i += PK_CELLS_WG) {
+        const u32 h0 = (i / nbx) * A.bh * PK_CELL_TILES_X + (i % nbx) * tw;
+        u32 s = 0;
+        for (u32 r = 0; r < A.bh; r++)
+            for (u32 c = 0; c < tw; c++) s += hb[h0 + r * PK_CELL_TILES_X + c];
+        const u32 q = s * A.levels / div;       // s * levels <= 3 * 23,040 * 256 < 2^25
+        if (A.cells) A.cells[(size_t)e * nblk + i] = (u8)q;
+        acc += pk_arch_mix(PK_CELL_GOLD * (i + 1u) + q);
+    }
+    red[tid] = acc;
+    __syncthreads();
+    const u32 span = PK_CELLS_WG / 8u;
+    if (tid < 8u) {
+        u64 s = 0;
+        for (u32 j = 0; j < span; j++) s += red[tid * span + j];
+        red[tid * span] = s;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        u64 sum = 0;
+        for (u32 j = 0; j < 8u; j++) sum += red[j * span];
+        const u64 salt = A.salt ? A.salt[e] : 0;
+        if (A.salt) sum += pk_arch_mix(salt);
+        u64 key = pk_arch_mix(sum);
+        if (key == PK_ARCH_NOKEY) key = PK_ARCH_NOKEY - 1u;
+        if (A.salt && salt == PK_ARCH_NOKEY) key = PK_ARCH_NOKEY;   // "no cell" passes through
+        A.keys[e] = key;
+    }
+}
+
+hipError_t pk_launch_frame_keys(const PkCellArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(PK_K1_KERNEL_FRAME_KEYS, dim3(a.env1 - a.env0), dim3(PK_CELLS_WG), 0, s, a);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------------------
 // Archive exchange (pk_archive_pack / pk_archive_merge): cells as records and whole-slot payloads.
 

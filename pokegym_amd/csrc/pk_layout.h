@@ -310,3 +310,19 @@ struct PkPackArgs {
     uint32_t* n_payloads_out;    // caller's word, or null
     uint32_t cell0, count, max_payloads, delta;
 };
+
+// Frame cells (pk_frame_keys): a screen is PK_CELL_PIECES 16-byte pieces, ten to a row, each piece two
+// halves of 8 pixels; an 8 x 8 tile is the same half of eight pieces, ten rows of pieces apart
+#define PK_CELL_PIECES (PK_SCREEN / 16u)      // 1,440
+#define PK_CELL_TILES_X (PK_COLS / 8u)        // 20
+#define PK_CELL_TILES (PK_SCREEN / 64u)       // 360, also the most blocks a screen has
+#define PK_CELL_GOLD 0x9E3779B97F4A7C15ull
+
+struct PkCellArgs {
+    const uint8_t* screen;       // [..][144][160], 16-byte aligned: the handle's or the caller's
+    const uint64_t* salt;        // caller's [n] or null; may be keys
+    uint64_t* keys;              // caller's [n]
+    uint8_t* cells;              // caller's [n][nbx * nby] or null
+    uint32_t env0, env1;
+    uint32_t bw, bh, levels;
+};

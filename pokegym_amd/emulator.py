@@ -264,6 +264,40 @@ class BatchedEmulator:
                                    self._stream()), "pk_cell_keys")
         return out
 
+    def frame_cells(self, bw: int = 16, bh: int = 16) -> int:
+        """Blocks of bw x bh pixels a screen has, (160 / bw) * (144 / bh); 0 for a pair frame_keys
+        does not take (pk_frame_cells)."""
+        return int(self._L.pk_frame_cells(int(bw), int(bh)))
+
+    def frame_keys(self, bw: int = 16, bh: int = 16, levels: int = 8, screen: torch.Tensor | None = None,
+                   salt: torch.Tensor | None = None, out: torch.Tensor | None = None, cells: torch.Tensor | None = None,
+                   env0: int = 0, count: int | None = None):
+        """int64 (n,) cell keys of the envs' frames, downscaled to blocks of bw x bh pixels and
+        quantised to `levels` levels (pk_frame_keys, on the current stream); the rest of `out` is
+        untouched.  screen: a uint8 (n, 144, 160) tensor to read in the place of the emulator's own
+        screen (which needs render=True).  salt: int64 (n,) words mixed into the keys, e.g.
+        cell_keys() — `out` itself will do; a salt of -1 ("no cell") stays -1.  cells: a uint8
+        (n, frame_cells(bw, bh)) tensor that receives the cell image of the range's envs."""
+        if out is None:
+            out = torch.zeros(self.n, dtype=torch.int64, device=self.device)
+        count = self.n - env0 if count is None else count
+        sp = cp = None
+        if screen is not None:
+            if (screen.dtype != torch.uint8 or screen.device != self.device or tuple(screen.shape) != (self.n, ROWS, COLS)
+                    or not screen.is_contiguous()):
+                raise ValueError("screen must be a contiguous uint8 (n_envs, 144, 160) tensor on the emulator's device")
+            sp = ctypes.c_void_p(screen.data_ptr())
+        if cells is not None:
+            c = self.frame_cells(bw, bh)
+            if (cells.dtype != torch.uint8 or cells.device != self.device or not cells.is_contiguous()
+                    or (c and tuple(cells.shape) != (self.n, c))):
+                raise ValueError("cells must be a contiguous uint8 (n_envs, frame_cells(bw, bh)) tensor on the emulator's device")
+            cp = ctypes.c_void_p(cells.data_ptr())
+        check(self._L.pk_frame_keys(self._h, int(bw), int(bh), int(levels), sp, self._full(salt, torch.int64, "salt"),
+                                    self._full(out, torch.int64, "keys"), cp, env0, count, self._stream()),
+              "pk_frame_keys")
+        return out
+
     def archive_update(self, keys: torch.Tensor, scores: torch.Tensor, mask: torch.Tensor | None = None,
                        env0: int = 0, count: int | None = None, out: torch.Tensor | None = None):
         """Enter the envs of the range into the archive under keys (int64: the 64 key bits; -1 is the

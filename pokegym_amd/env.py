@@ -246,7 +246,8 @@ class VecEnv:
                  heatmap: bool = False, reward: bool = True, power_on: bool = False, batch_size: int | None = None,
                  state_pool=None, pool_seed: int = 0, bank_slots: int = 0, bank_episodes: bool = False,
                  fork_slots: int = 0, archive_cells: int = 0, archive_seed: int = 0, archive_shift: int = 0,
-                 record_trajectories: bool = False, archive_exchange: bool = False):
+                 record_trajectories: bool = False, archive_exchange: bool = False, archive_key: str = "ram",
+                 archive_frame=(16, 16, 8)):
         """reward=False: the screen-obs env of configs[3] — obs is the (144, 160) u8 screen, rewards are
         0 and episodes end at max_episode_steps.  power_on=True starts (and resets) every env from
         the cartridge's power-on state instead of a savestate.
@@ -269,7 +270,12 @@ class VecEnv:
         archive_cells=K (needs bank_episodes=True) adds K more slots after those and an exploration
         archive over them (pk_archive_*): archive_update() keeps the best episode per cell key,
         archive_explore(mask) resumes envs from cells drawn by visit count with archive_seed;
-        archive_shift is cell_keys()'s coordinate shift.  Both are calls of the training loop between
+        archive_shift is cell_keys()'s coordinate shift.  archive_key chooses what a cell is: "ram" (the
+        default) is pk_cell_keys' map | x | y | badges of Pokémon Red's WRAM; "frame" is Go-Explore's
+        downscaled frame (pk_frame_keys), which any cartridge has and which tells a menu, a battle or a
+        dialogue from the map under it; "frame+ram" is both, the RAM key mixed into the frame key as its
+        salt.  archive_frame = (bw, bh, levels) is the frame cell's block size and level count;
+        frame_cells() returns the cell image itself.  Both are calls of the training loop between
         steps: the auto-reset path does not explore, and the archive is not driven per sub-batch
         on the sub-batch streams.  archive_exchange=True (needs archive_cells) lets the archive leave
         the handle: archive_export() / archive_import() move its cells — records, whole slots and this
@@ -354,6 +360,18 @@ class VecEnv:
         if self.fork_slots and not bank_episodes:
             raise ValueError("fork_slots needs bank_episodes=True")
         self.archive_cells, self.archive_shift = int(archive_cells), int(archive_shift)
+        if archive_key not in ("ram", "frame", "frame+ram"):
+            raise ValueError(f'archive_key must be "ram", "frame" or "frame+ram", not {archive_key!r}')
+        try:
+            bw, bh, levels = (int(v) for v in archive_frame)
+        except (TypeError, ValueError):
+            raise ValueError("archive_frame must be (bw, bh, levels)") from None
+        if bw not in (8, 16, 32, 40, 80, 160) or bh not in (8, 16, 24, 48, 72, 144) or not 2 <= levels <= 256:
+            raise ValueError("archive_frame = (bw, bh, levels): bw a multiple of 8 that divides 160, bh one that "
+                             "divides 144, levels in 2..256")
+        if archive_key != "ram" and not getattr(emulator, "render", True):
+            raise ValueError(f'archive_key="{archive_key}" reads the screen: the emulator needs render=True')
+        self.archive_key, self.archive_frame = archive_key, (bw, bh, levels)
         self._arch0 = 0             # first slot of the archive's cells
         self._arch_out = None
         self.archive_exchange = bool(archive_exchange)
@@ -536,9 +554,27 @@ class VecEnv:
         out[self._phys] = values
         return out
 
+    def _cell_keys(self) -> torch.Tensor:
+        """The keys archive_key names, in emulator order."""
+        if self.archive_key == "ram":
+            return self.emu.cell_keys(self.archive_shift)
+        salt = self.emu.cell_keys(self.archive_shift) if self.archive_key == "frame+ram" else None
+        return self.emu.frame_keys(*self.archive_frame, salt=salt, out=salt)
+
     def cell_keys(self) -> torch.Tensor:
-        """The cell key of every env (int64, env order): pk_cell_keys with archive_shift."""
-        return self._logical(self.emu.cell_keys(self.archive_shift))
+        """The cell key of every env (int64, env order) as archive_key has it: pk_cell_keys with
+        archive_shift, pk_frame_keys with archive_frame, or the second salted with the first."""
+        return self._logical(self._cell_keys())
+
+    def frame_cells(self) -> torch.Tensor:
+        """The frame cell image of every env, uint8 (num_envs, C) in env order: the screen in blocks of
+        archive_frame's size, each quantised to its levels (pk_frame_keys' cells_dev) — a small global
+        observation, and what the "frame" keys are made of.  On the current stream after a pipeline join."""
+        self._join_streams()
+        bw, bh, levels = self.archive_frame
+        cells = torch.zeros((self.emu.n, self.emu.frame_cells(bw, bh)), dtype=torch.uint8, device=self.device)
+        self.emu.frame_keys(bw, bh, levels, cells=cells)
+        return self._logical(cells)
 
     def archive_update(self, scores=None, keys=None, mask=None) -> torch.Tensor:
         """Enter every env (those with mask[e] != 0) into the archive: scores default to the running
@@ -550,7 +586,7 @@ class VecEnv:
             raise RuntimeError("VecEnv(archive_cells=...) keeps the archive")
         self._join_streams()
         scores = self._physical(self.stats.ep_return if scores is None else scores, float("nan"), torch.float64)
-        keys = self.emu.cell_keys(self.archive_shift) if keys is None else self._physical(keys, -1, torch.int64)
+        keys = self._cell_keys() if keys is None else self._physical(keys, -1, torch.int64)
         # padding envs never take part: their mask byte is 0
         mask = self._physical(torch.ones(self.num_envs, dtype=torch.uint8, device=self.device) if mask is None
                               else torch.as_tensor(mask, device=self.device) != 0, 0, torch.uint8)
