@@ -39,6 +39,8 @@
  *                    whole-slot payloads, and their merge into the archive of another handle
  *   pk_frame_keys    no reference equivalent: Go-Explore's cell of a frame, the screen downscaled to a
  *                    few blocks and quantised to a few levels, as a 64-bit key for the archive
+ *   pk_counts_update / pk_counts_pack / pk_counts_add   no reference equivalent: a table key -> visit count
+ *                    on the device and the count-based bonus beta / sqrt(count) of every env's key
  * With PK_F_REWARD, pk_step also runs the reward stack of Environment.step
  * (environment.py:1338-1612) and pk_reset follows Environment.reset (:1233-1334).
  */
@@ -514,6 +516,78 @@ int pk_archive_pack(pk_handle* h, uint32_t flags, uint32_t cell0, uint32_t count
                     pk_xrec* rec_dev, uint8_t* payload_dev, uint32_t* n_payloads_dev, void* stream);
 int pk_archive_merge(pk_handle* h, const pk_xrec* rec_dev, uint32_t n_records, const uint8_t* payload_dev,
                      uint32_t n_payloads, int32_t* cell_out_dev, void* stream);
+
+/* Visit counts: a persistent table key -> count on the device, for a count-based exploration bonus
+ * (Tang et al., "#Exploration") over any 64-bit key — pk_frame_keys' frame cell on any cartridge,
+ * pk_cell_keys on Pokémon Red.  Every env of a range counts its key and gets the key's new count and
+ * beta / sqrt(count) back, stream-ordered and without a host sync.  It needs nothing else: no
+ * PK_F_REWARD, no bank, no archive.
+ *
+ * pk_counts_create (synchronous): once per handle, on any handle; cap_log2 in 10..30.  The table has
+ * 2^cap_log2 entries of {key u64, count u64, sent u64} (24 bytes each, plus 4 bytes per env) and takes
+ * limit = 3 * 2^(cap_log2 - 2) distinct keys: pk_counts_limit, 0 without a table.  On failure (second
+ * call, bad cap_log2, limit < n_envs, out of memory) the handle is unchanged.  Every other counts call
+ * on a handle without a table fails with a negative code and does nothing.  A handle that never
+ * creates a table makes exactly the launches and allocations it made before.
+ *
+ * Placement: an entry's probe starts at the low cap_log2 bits of mix(key), mix splitmix64's finaliser
+ * (pk_archive_explore above); probing is linear, to the next entry, and wraps from the last entry
+ * to entry 0.  Where a key sits is not observable; the rule is stated so that a test can build keys
+ * that share a probe sequence.
+ *
+ * pk_counts_update (stream-ordered, never a host sync, no allocation, two launches): keys_dev u64[n],
+ * mask_dev u8[n] or NULL (= every env), counts_out_dev u64[n] or NULL, bonus_out_dev f64[n] or NULL,
+ * full size and indexed by env; the range follows pk_step_range's rule.  The participants P are the
+ * envs of the range whose mask byte is not 0 and whose key is not UINT64_MAX (reserved, as in the
+ * archive: "no cell").  With `used` the distinct keys stored when the call starts, the call is open
+ * when used + count <= limit — count the size of the range, not of P — and closed otherwise.
+ *   - open: every key of P that is not stored is inserted with count 0, and used rises by their number;
+ *   - closed: nothing is inserted; a participant whose key is not stored adds 1 to overflow and gets
+ *     count 0 and bonus 0.0, the keys that are stored are counted as usual.
+ * A call thus admits all of its new keys or none, whatever the order of its envs, and used never
+ * exceeds limit.  With c0(k) the stored count of key k and m(k) the participants that hold k, the new
+ * count is c(k) = c0(k) + m(k), and every participant e that holds k gets
+ *   counts_out[e] = c(k),  bonus_out[e] = beta / sqrt((double)c(k))        IEEE f64, correctly rounded
+ * The other envs of the range get 0 and 0.0; nothing outside the range is written.
+ * PK_COUNTS_PEEK: the table, used and overflow stay as they are; the outputs are those of c0 (0 and 0.0
+ * for a key that is not stored).
+ *
+ * pk_counts_add (stream-ordered, no allocation): the same rule over records, c(k) += rec.count.  rec_dev
+ * is a device pk_crec[n_records], 16-byte aligned, n_records in 1..2^30.  A record with key UINT64_MAX
+ * or count 0 is skipped.  The call is open when used + n_records <= limit; when closed, every record
+ * whose key is not stored adds 1 to overflow.  PK_COUNTS_FOREIGN raises the key's sent word by the
+ * same amount: counts that came from another handle are never sent on (pk_archive_merge's rule).
+ *
+ * pk_counts_pack (stream-ordered, one launch): one record per stored key whose packed count is not 0.
+ * The packed count is the key's count, or with PK_COUNTS_DELTA count - sent, after which sent = count:
+ * what this handle counted itself since its last delta pack.  The order of the records is
+ * unspecified, their set is fixed.  rec_dev is a device pk_crec[max_records], 16-byte aligned;
+ * *n_out_dev (device u32, required) receives the number written.  max_records < pk_counts_limit is
+ * refused, so a pack is never cut short.
+ *
+ * pk_counts_read (synchronous): the distinct keys stored and the overflow count (not cleared by
+ * reading); either pointer may be NULL.  pk_counts_clear (stream-ordered): the table is empty again,
+ * used and overflow 0.
+ *
+ * Ordering: the table is one shared structure; the caller orders the calls that touch it, as for the
+ * archive: calls over different ranges are allowed, but not concurrently.  Everything observable
+ * — counts, bonuses, used, overflow, the set a pack writes — is the same from run to run.  Bad
+ * arguments (no table, NULL keys_dev or rec_dev, a range past n, an env0 that is no multiple of 64,
+ * n_records out of range, a misaligned rec_dev, unknown flag bits) are a negative code with
+ * pk_last_error, never a fault, and write nothing. */
+#define PK_COUNTS_PEEK 1u      /* pk_counts_update: read only */
+#define PK_COUNTS_FOREIGN 1u   /* pk_counts_add: counts that came from another handle */
+#define PK_COUNTS_DELTA 1u     /* pk_counts_pack: only what this handle counted itself since the last delta pack */
+typedef struct pk_crec { uint64_t key, count; } pk_crec;      /* 16 bytes */
+int pk_counts_create(pk_handle* h, uint32_t cap_log2);
+uint64_t pk_counts_limit(const pk_handle* h);
+int pk_counts_update(pk_handle* h, const uint64_t* keys_dev, const uint8_t* mask_dev, uint32_t env0, uint32_t count,
+                     double beta, uint32_t flags, uint64_t* counts_out_dev, double* bonus_out_dev, void* stream);
+int pk_counts_add(pk_handle* h, const pk_crec* rec_dev, uint32_t n_records, uint32_t flags, void* stream);
+int pk_counts_pack(pk_handle* h, uint32_t flags, pk_crec* rec_dev, uint64_t max_records, uint32_t* n_out_dev,
+                   void* stream);
+int pk_counts_read(pk_handle* h, uint64_t* used, uint64_t* overflow);
+int pk_counts_clear(pk_handle* h, void* stream);
 
 /* Emulated instructions executed by the last pk_step, summed over envs (synchronous). */
 int pk_last_instr_count(pk_handle* h, uint64_t* out);

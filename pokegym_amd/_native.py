@@ -21,6 +21,9 @@ PK_TRAJ_BROKEN = 1
 PK_TRAJ_OVERFLOW = 2
 PK_TRAJ_EMPTY = 4
 PK_XCHG_DELTA = 1
+PK_COUNTS_PEEK = 1
+PK_COUNTS_FOREIGN = 1
+PK_COUNTS_DELTA = 1
 HEAT_SHAPE = (444, 436)
 OBS_SHAPE = (72, 80, 4)
 # PK_ERR_* -> the exception the reference raises at that point (include/pokegym_amd.h)
@@ -44,7 +47,9 @@ EXPORTS = ("pk_create", "pk_destroy", "pk_last_error", "pk_abi_version", "pk_res
            "pk_traj_enable", "pk_traj_capacity", "pk_traj_get", "pk_bank_traj_get",
            "pk_archive_exchange_enable", "pk_archive_payload_bytes", "pk_archive_format", "pk_archive_pack",
            "pk_archive_merge",
-           "pk_frame_cells", "pk_frame_keys")
+           "pk_frame_cells", "pk_frame_keys",
+           "pk_counts_create", "pk_counts_limit", "pk_counts_update", "pk_counts_add", "pk_counts_pack",
+           "pk_counts_read", "pk_counts_clear")
 
 
 class PkConfig(ctypes.Structure):
@@ -131,6 +136,7 @@ def bind(L):
     bind_v10(L)
     bind_v11(L)
     bind_v12(L)
+    bind_counts(L)
 
 
 def bind_v2(L):
@@ -228,6 +234,21 @@ def bind_v12(L):
     L.pk_frame_cells.argtypes = [u32, u32]
     L.pk_frame_cells.restype = u32
     L.pk_frame_keys.argtypes = [vp, u32, u32, u32, vp, vp, vp, vp, u32, u32, vp]
+
+
+def bind_counts(L):
+    """argtypes of the visit counts (additive to ABI v12; shared with the host-simulation test build)."""
+    vp = ctypes.c_void_p
+    u32 = ctypes.c_uint32
+    u64 = ctypes.c_uint64
+    L.pk_counts_create.argtypes = [vp, u32]
+    L.pk_counts_limit.argtypes = [vp]
+    L.pk_counts_limit.restype = u64
+    L.pk_counts_update.argtypes = [vp, vp, vp, u32, u32, ctypes.c_double, u32, vp, vp, vp]
+    L.pk_counts_add.argtypes = [vp, vp, u32, u32, vp]
+    L.pk_counts_pack.argtypes = [vp, u32, vp, u64, vp, vp]
+    L.pk_counts_read.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    L.pk_counts_clear.argtypes = [vp, vp]
 
 
 def check(rc: int, what: str):

@@ -51,6 +51,9 @@ hipError_t pk_launch_arch_out(const PkArchArgs& a, hipStream_t s);
 hipError_t pk_launch_cell_keys(const uint8_t* mem, uint32_t sh, uint32_t shift, uint64_t* keys, uint32_t env0,
                                uint32_t env1, hipStream_t s);
 hipError_t pk_launch_frame_keys(const PkCellArgs& a, hipStream_t s);
+hipError_t pk_launch_cnt_update(const PkCountArgs& a, hipStream_t s);
+hipError_t pk_launch_cnt_add(const PkCountArgs& a, hipStream_t s);
+hipError_t pk_launch_cnt_pack(const PkCountArgs& a, hipStream_t s);
 hipError_t pk_launch_traj_record(const PkTrajArgs& a, hipStream_t s);
 hipError_t pk_launch_traj_reset(const PkTrajArgs& a, hipStream_t s);
 hipError_t pk_launch_traj_mark(const PkTrajArgs& a, hipStream_t s);
@@ -328,6 +331,10 @@ struct pk_handle {
     uint8_t* bt_act = nullptr;
     int32_t* bt_origin = nullptr;
     uint32_t* bt_flags = nullptr;
+    // visit counts (pk_counts_create; pk_layout.h PkCountArgs), cnt_log2 = 0 without a table: the
+    // header words, the three arrays of the table and the per-env entry words of an update
+    uint32_t cnt_log2 = 0;
+    uint8_t* c_fix = nullptr;
     // profiling: 4 events per profiled step (start, after K1, after K2, after K4+K3)
     bool prof = false;
     std::vector<hipEvent_t> ev_pool;
@@ -369,7 +376,8 @@ void pk_destroy(pk_handle* h) {
                     h->lists, h->dbg, h->info, h->info_flag, h->heat, h->info_bits, h->bank_slot_s, h->slot_bank_s,
                     h->b_mem, h->b_regs, h->b_lat, h->b_screen, h->b_filled, h->b_rejects, h->b_lists, h->b_src,
                     h->e_fields, h->e_seen, h->e_mask, h->e_cutc, h->b_ep_filled, h->a_fix, h->a_ones, h->a_zero,
-                    h->x_fix, h->x_ones, h->x_zero, h->t_act, h->t_origin, h->t_flags, h->bt_act, h->bt_origin, h->bt_flags};
+                    h->x_fix, h->x_ones, h->x_zero, h->t_act, h->t_origin, h->t_flags, h->bt_act, h->bt_origin, h->bt_flags,
+                    h->c_fix};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     delete h;
@@ -1926,6 +1934,130 @@ int pk_bank_traj_get(pk_handle* h, uint32_t slot0, uint32_t count, int32_t* orig
     if (count == 0 || (uint64_t)slot0 + count > h->bank_n)
         return fail(-EINVAL, "slots [%u, +%u) are not inside the bank's %u", slot0, count, h->bank_n);
     return traj_get(h, true, slot0, count, origin, len, flags, actions, stream);
+}
+
+// ---- visit counts -------------------------------------------------------------------------------
+
+static uint64_t counts_limit(uint32_t lg) { return 3ull << (lg - 2u); }
+
+// c_fix: header | keys | counts | sent | per-env entry words
+static PkCountArgs counts_args(const pk_handle* h) {
+    PkCountArgs a;
+    memset(&a, 0, sizeof a);
+    const size_t cap = (size_t)1 << h->cnt_log2;
+    a.hdr = (uint64_t*)h->c_fix;
+    a.c_key = a.hdr + PK_CH_WORDS;
+    a.c_cnt = a.c_key + cap;
+    a.c_sent = a.c_cnt + cap;
+    a.tgt = (uint32_t*)(a.c_sent + cap);
+    a.c_mask = (uint32_t)(cap - 1u);
+    a.limit = counts_limit(h->cnt_log2);
+    return a;
+}
+
+static hipError_t counts_wipe(const pk_handle* h, hipStream_t s) {
+    const PkCountArgs a = counts_args(h);
+    const size_t cap = (size_t)a.c_mask + 1u;
+    hipError_t e = hipMemsetAsync(a.hdr, 0, PK_CH_WORDS * 8, s);
+    if (e == hipSuccess) e = hipMemsetAsync(a.c_key, 0xFF, cap * 8, s);
+    if (e == hipSuccess) e = hipMemsetAsync(a.c_cnt, 0, cap * 16, s);
+    return e;
+}
+
+uint64_t pk_counts_limit(const pk_handle* h) { return h && h->cnt_log2 ? counts_limit(h->cnt_log2) : 0; }
+
+int pk_counts_create(pk_handle* h, uint32_t cap_log2) {
+    if (!h) return fail(-EINVAL, "null handle");
+    if (h->cnt_log2) return fail(-EEXIST, "the handle already has a count table of 2^%u entries", h->cnt_log2);
+    if (cap_log2 < PK_CNT_MIN_LOG2 || cap_log2 > PK_CNT_MAX_LOG2)
+        return fail(-EINVAL, "cap_log2 must be %u..%u", PK_CNT_MIN_LOG2, PK_CNT_MAX_LOG2);
+    if (counts_limit(cap_log2) < h->n)
+        return fail(-EINVAL, "a table of 2^%u entries takes %llu keys, fewer than the handle's %u envs", cap_log2,
+                    (unsigned long long)counts_limit(cap_log2), h->n);
+    HIPCHK(hipSetDevice(h->device));
+    const size_t bytes = PK_CH_WORDS * 8 + ((size_t)24 << cap_log2) + (size_t)h->npad * 4;
+    uint8_t* p = nullptr;
+    hipError_t e = hipMalloc((void**)&p, bytes);
+    if (e == hipSuccess) {
+        h->c_fix = p;
+        h->cnt_log2 = cap_log2;
+        e = counts_wipe(h, nullptr);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+    }
+    if (e != hipSuccess) {
+        if (p) (void)hipFree(p);
+        h->c_fix = nullptr;
+        h->cnt_log2 = 0;
+        (void)hipGetLastError();
+        return fail(-ENOMEM, "count table of 2^%u entries (%zu bytes): %s", cap_log2, bytes, hipGetErrorString(e));
+    }
+    return 0;
+}
+
+int pk_counts_update(pk_handle* h, const uint64_t* keys, const uint8_t* mask, uint32_t env0, uint32_t count, double beta,
+                     uint32_t flags, uint64_t* counts_out, double* bonus_out, void* stream) {
+    int rc;
+    if ((rc = check_range(h, env0, count))) return rc;
+    if (!h->cnt_log2) return fail(-ENOENT, "the handle has no count table (pk_counts_create)");
+    if (!keys) return fail(-EINVAL, "keys_dev is required");
+    if (flags & ~PK_COUNTS_PEEK) return fail(-EINVAL, "unknown flags 0x%x", flags);
+    HIPCHK(hipSetDevice(h->device));
+    PkCountArgs a = counts_args(h);
+    a.keys = keys; a.mask = mask; a.counts_out = counts_out; a.bonus_out = bonus_out;
+    a.env0 = env0; a.env1 = env0 + count; a.beta = beta; a.peek = flags & PK_COUNTS_PEEK;
+    HIPCHK(pk_launch_cnt_update(a, (hipStream_t)stream));
+    return 0;
+}
+
+int pk_counts_add(pk_handle* h, const pk_crec* rec, uint32_t n_records, uint32_t flags, void* stream) {
+    if (!h) return fail(-EINVAL, "null handle");
+    if (!h->cnt_log2) return fail(-ENOENT, "the handle has no count table (pk_counts_create)");
+    if (!rec || ((uintptr_t)rec & 15u)) return fail(-EINVAL, "rec_dev is required and must be 16-byte aligned");
+    if (n_records == 0 || n_records > (1u << 30)) return fail(-EINVAL, "n_records must be 1..2^30");
+    if (flags & ~PK_COUNTS_FOREIGN) return fail(-EINVAL, "unknown flags 0x%x", flags);
+    HIPCHK(hipSetDevice(h->device));
+    PkCountArgs a = counts_args(h);
+    a.rec = rec; a.env1 = n_records; a.foreign = flags & PK_COUNTS_FOREIGN;
+    HIPCHK(pk_launch_cnt_add(a, (hipStream_t)stream));
+    return 0;
+}
+
+int pk_counts_pack(pk_handle* h, uint32_t flags, pk_crec* rec, uint64_t max_records, uint32_t* n_out, void* stream) {
+    if (!h) return fail(-EINVAL, "null handle");
+    if (!h->cnt_log2) return fail(-ENOENT, "the handle has no count table (pk_counts_create)");
+    if (!rec || ((uintptr_t)rec & 15u)) return fail(-EINVAL, "rec_dev is required and must be 16-byte aligned");
+    if (!n_out) return fail(-EINVAL, "n_out_dev is required");
+    if (max_records < counts_limit(h->cnt_log2))
+        return fail(-EINVAL, "max_records %llu: a pack needs room for the table's limit of %llu records",
+                    (unsigned long long)max_records, (unsigned long long)counts_limit(h->cnt_log2));
+    if (flags & ~PK_COUNTS_DELTA) return fail(-EINVAL, "unknown flags 0x%x", flags);
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    PkCountArgs a = counts_args(h);
+    a.pack = rec; a.n_out = n_out; a.max_records = max_records; a.delta = flags & PK_COUNTS_DELTA;
+    HIPCHK(hipMemsetAsync(n_out, 0, 4, s));
+    HIPCHK(pk_launch_cnt_pack(a, s));
+    return 0;
+}
+
+int pk_counts_read(pk_handle* h, uint64_t* used, uint64_t* overflow) {
+    if (!h) return fail(-EINVAL, "null handle");
+    if (!h->cnt_log2) return fail(-ENOENT, "the handle has no count table (pk_counts_create)");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipDeviceSynchronize());
+    uint64_t hdr[PK_CH_WORDS];
+    HIPCHK(hipMemcpy(hdr, h->c_fix, sizeof hdr, hipMemcpyDeviceToHost));
+    if (used) *used = hdr[PK_CH_USED];
+    if (overflow) *overflow = hdr[PK_CH_OVERFLOW];
+    return 0;
+}
+
+int pk_counts_clear(pk_handle* h, void* stream) {
+    if (!h) return fail(-EINVAL, "null handle");
+    if (!h->cnt_log2) return fail(-ENOENT, "the handle has no count table (pk_counts_create)");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(counts_wipe(h, (hipStream_t)stream));
+    return 0;
 }
 
 }  // extern "C"

@@ -1048,3 +1048,210 @@ hipError_t pk_launch_xchg_move(const PkXchgArgs& x, bool pack, hipStream_t s) {
     else hipLaunchKernelGGL((pk_xchg_move_kernel<false>), dim3(grid), dim3(256), 0, s, x);
     return hipGetLastError();
 }
+
+// ---------------------------------------------------------------------------------------------
+// Visit counts (pk_counts_*): a persistent table key -> count, counted into by every env of a range
+// and read back as the count-based bonus beta / sqrt(count) (include/pokegym_amd.h states the
+// model).  Sums and a 64-bit compare-and-swap on the key word only: nothing depends on the order of
+// threads.  Whether a call may insert is decided by one word no thread of the call writes (USED, the
+// keys stored when the call started), so a full table admits all new keys of a call or none; the
+// keys a call inserts are counted aside (NEW) and the commit that ends the call adds them up.  The
+// table is never more than three quarters full, so a probe loop ends at an empty entry.
+
+// one atomic per wave for a count every lane may add 1 to; every lane of the wave calls it
+__device__ static inline void pk_cnt_tally(bool mine, u64* word) {
+    const u64 m = __builtin_amdgcn_ballot_w64(mine);
+    if (m && pk_lane() == (u32)__builtin_ffsll((long long)m) - 1u)
+        atomicAdd(reinterpret_cast<ull*>(word), (ull)__builtin_popcountll(m));
+}
+
+// A key word as other threads may be swapping it in.  A key word only ever goes from empty to its
+// final key, so a plain load is enough on the device: a stale "empty" leads to the compare-and-swap,
+// which returns the truth, and any other value is final.  The host simulation runs workgroups on
+// concurrent host threads, where the same read has to be an atomic load to be defined at all.
+__device__ static inline u64 pk_cnt_peek(const ull* p) {
+#ifndef __HIPCC__
+    return __atomic_load_n(p, __ATOMIC_RELAXED);
+#else
+    return *p;
+#endif
+}
+
+// The entry of key: found, or — in a call that may insert — claimed by a compare-and-swap on the
+// first empty entry of its probe sequence (made = this thread's swap made it).  PK_ARCH_NONE when
+// the key is absent and stays so.
+__device__ static inline u32 pk_cnt_find(const PkCountArgs& A, u64 key, bool insert, bool& made) {
+    u32 pos = (u32)pk_arch_mix(key) & A.c_mask;
+    for (u32 p = 0; p <= A.c_mask; p++, pos = (pos + 1u) & A.c_mask) {
+        ull* ck = reinterpret_cast<ull*>(A.c_key + pos);
+        u64 k = pk_cnt_peek(ck);
+        if (k == PK_ARCH_NOKEY) {
+            if (!insert) return PK_ARCH_NONE;
+            k = atomicCAS(ck, (ull)PK_ARCH_NOKEY, (ull)key);
+            if (k == PK_ARCH_NOKEY) {
+                made = true;
+                return pos;
+            }
+        }
+        if (k == key) return pos;
+    }
+    return PK_ARCH_NONE;
+}
+
+#ifndef PK_CNT_PRE
+#define PK_CNT_PRE PK_ARCH_PRE   // rounds of the wave pre-reduction (0: every lane adds alone, tools/measure_counts.py)
+#endif
+// launch one of pk_counts_update, thread = env: find or insert the key's entry, leave it in tgt, and
+// count the env.  The lanes of a wave that hold one entry add their number with one atomic (the
+// rounds of pk_arch_group; all 65,536 envs of a title screen hold one); a peek only finds.
+__global__ void __launch_bounds__(256) pk_cnt_claim_kernel(PkCountArgs A) {
+    const u32 e = A.env0 + blockIdx.x * blockDim.x + threadIdx.x;
+    const bool open = A.hdr[PK_CH_USED] + (A.env1 - A.env0) <= A.limit;
+    u32 t = PK_ARCH_NONE;
+    bool part = false, made = false;
+    if (e < A.env1 && (!A.mask || A.mask[e])) {
+        const u64 key = A.keys[e];
+        part = key != PK_ARCH_NOKEY;
+        if (part) t = pk_cnt_find(A, key, open && !A.peek, made);
+    }
+    if (e < A.env1) A.tgt[e] = t;
+    if (A.peek) return;
+    pk_cnt_tally(made, A.hdr + PK_CH_NEW);
+    pk_cnt_tally(part && t == PK_ARCH_NONE, A.hdr + PK_CH_OVERFLOW);
+    bool todo = t != PK_ARCH_NONE, match, lead;
+    u64 mm;
+    for (u32 it = 0; it <= PK_CNT_PRE; it++) {
+        u32 n = 1;
+        if (it < PK_CNT_PRE) {   // a group per round; after the last round every lane goes alone
+            if (!pk_arch_group(todo, t, match, lead, mm)) break;
+            n = (u32)__builtin_popcountll(mm);
+        } else {
+            match = lead = todo;
+        }
+        if (lead && match) atomicAdd(reinterpret_cast<ull*>(A.c_cnt + t), (ull)n);
+        todo = todo && !match;
+    }
+}
+
+// launch two, thread = env: the count of the env's entry and the bonus; the first thread commits
+// the call's new keys to USED
+__global__ void __launch_bounds__(256) pk_cnt_bonus_kernel(PkCountArgs A) {
+    const u32 e = A.env0 + blockIdx.x * blockDim.x + threadIdx.x;
+    if (e == A.env0 && !A.peek) {
+        A.hdr[PK_CH_USED] += A.hdr[PK_CH_NEW];
+        A.hdr[PK_CH_NEW] = 0;
+    }
+    if (e >= A.env1) return;
+    const u32 t = A.tgt[e];
+    const u64 c = t != PK_ARCH_NONE ? A.c_cnt[t] : 0;
+    if (A.counts_out) A.counts_out[e] = c;
+    if (A.bonus_out) A.bonus_out[e] = c ? A.beta / sqrt((double)c) : 0.0;
+}
+
+// pk_counts_add, thread = record: launch one of an update with records as items, each adding its own
+// count (to the sent word as well when the counts are foreign).  Records seldom share a key, so
+// only the two tallies are reduced per wave.
+__global__ void __launch_bounds__(256) pk_cnt_add_kernel(PkCountArgs A) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool open = A.hdr[PK_CH_USED] + A.env1 <= A.limit;
+    u32 t = PK_ARCH_NONE;
+    u64 c = 0;
+    bool part = false, made = false;
+    if (i < A.env1) {
+        const uint4 w = reinterpret_cast<const uint4*>(A.rec)[i];
+        const u64 key = w.x | (u64)w.y << 32;
+        c = w.z | (u64)w.w << 32;
+        part = key != PK_ARCH_NOKEY && c != 0;
+        if (part) t = pk_cnt_find(A, key, open, made);
+    }
+    pk_cnt_tally(made, A.hdr + PK_CH_NEW);
+    pk_cnt_tally(part && t == PK_ARCH_NONE, A.hdr + PK_CH_OVERFLOW);
+    if (t == PK_ARCH_NONE) return;
+    atomicAdd(reinterpret_cast<ull*>(A.c_cnt + t), (ull)c);
+    if (A.foreign) atomicAdd(reinterpret_cast<ull*>(A.c_sent + t), (ull)c);
+}
+
+// the commit that ends a pk_counts_add
+__global__ void pk_cnt_commit_kernel(PkCountArgs A) {
+    A.hdr[PK_CH_USED] += A.hdr[PK_CH_NEW];
+    A.hdr[PK_CH_NEW] = 0;
+}
+
+// pk_counts_pack: a record per stored key whose packed count is not zero, appended in no order.  A
+// workgroup takes chunks of 256 * PK_CNT_PACK_ITEMS entries, consecutive lanes consecutive entries;
+// every thread keeps its records in registers, a scan through LDS numbers the workgroup's records
+// and one atomic takes its rows: 2^22 entries are 2,048 atomics on the caller's word (one per wave
+// was 65,536 returning atomics on one address, and the whole of the call's time).  A delta pack moves
+// sent up to the count.
+#define PK_CNT_PACK_ITEMS 8u
+#define PK_K1_KERNEL_CNT_PACK pk_cnt_pack_kernel
+__global__ void __launch_bounds__(256) pk_cnt_pack_kernel(PkCountArgs A) {
+    __shared__ u32 sums[256];
+    __shared__ u32 first;
+    const u64 cap = (u64)A.c_mask + 1u;
+    const u32 tid = threadIdx.x, per = 256u * PK_CNT_PACK_ITEMS;
+    const u32 nchunks = (u32)((cap + per - 1u) / per);
+    for (u32 ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
+        u64 key[PK_CNT_PACK_ITEMS], v[PK_CNT_PACK_ITEMS];
+        u32 mine = 0;
+#pragma unroll
+        for (u32 j = 0; j < PK_CNT_PACK_ITEMS; j++) {
+            const u64 p = (u64)ch * per + j * 256u + tid;
+            key[j] = p < cap ? A.c_key[p] : PK_ARCH_NOKEY;
+        }
+#pragma unroll
+        for (u32 j = 0; j < PK_CNT_PACK_ITEMS; j++) {
+            const u64 p = (u64)ch * per + j * 256u + tid;
+            v[j] = 0;
+            if (key[j] != PK_ARCH_NOKEY) {
+                const u64 c = A.c_cnt[p];
+                v[j] = c;
+                if (A.delta) {
+                    v[j] = c - A.c_sent[p];
+                    if (v[j]) A.c_sent[p] = c;
+                }
+            }
+            mine += v[j] ? 1u : 0u;
+        }
+        sums[tid] = mine;
+        __syncthreads();
+        for (u32 o = 1; o < 256u; o <<= 1) {
+            const u32 x = tid >= o ? sums[tid - o] : 0u;
+            __syncthreads();
+            sums[tid] += x;
+            __syncthreads();
+        }
+        if (tid == 255u) first = sums[255] ? atomicAdd(A.n_out, sums[255]) : 0u;
+        __syncthreads();
+        u64 row = (u64)first + sums[tid] - mine;
+#pragma unroll
+        for (u32 j = 0; j < PK_CNT_PACK_ITEMS; j++) {
+            if (!v[j]) continue;
+            if (row < A.max_records)
+                reinterpret_cast<uint4*>(A.pack)[row] =
+                    make_uint4((u32)key[j], (u32)(key[j] >> 32), (u32)v[j], (u32)(v[j] >> 32));
+            row++;
+        }
+        __syncthreads();   // sums and first are the next chunk's
+    }
+}
+
+static inline dim3 pk_cnt_grid(uint64_t items) { return dim3((u32)((items + 255u) / 256u)); }
+
+hipError_t pk_launch_cnt_update(const PkCountArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(pk_cnt_claim_kernel, pk_cnt_grid(a.env1 - a.env0), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(pk_cnt_bonus_kernel, pk_cnt_grid(a.env1 - a.env0), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t pk_launch_cnt_add(const PkCountArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(pk_cnt_add_kernel, pk_cnt_grid(a.env1), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(pk_cnt_commit_kernel, dim3(1), dim3(1), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t pk_launch_cnt_pack(const PkCountArgs& a, hipStream_t s) {
+    const uint64_t per = 256u * PK_CNT_PACK_ITEMS, chunks = ((uint64_t)a.c_mask + per) / per;
+    hipLaunchKernelGGL(PK_K1_KERNEL_CNT_PACK, dim3(chunks < 8192u ? (u32)chunks : 8192u), dim3(256), 0, s, a);
+    return hipGetLastError();
+}

@@ -326,3 +326,34 @@ struct PkCellArgs {
     uint32_t env0, env1;
     uint32_t bw, bh, levels;
 };
+
+// Visit counts (pk_counts_*): an open-addressing table key -> count of c_mask + 1 entries, linear
+// probing from the low bits of pk_arch_mix(key), in three arrays so that a probe reads keys only.
+// The header words: the distinct keys stored when the running call started (USED: what decides
+// whether the call is open, written only by the commit that ends a call), the keys the running
+// call has inserted so far (NEW) and the overflow count.  tgt holds, per env of an update, the entry
+// launch one found or made for the env's key, for launch two to read the count from.
+#define PK_CNT_MIN_LOG2 10u
+#define PK_CNT_MAX_LOG2 30u
+enum { PK_CH_USED = 0, PK_CH_OVERFLOW, PK_CH_NEW, PK_CH_WORDS = 8 };
+
+struct PkCountArgs {
+    uint64_t* hdr;               // [PK_CH_WORDS]
+    uint64_t* c_key;             // [c_mask + 1] PK_ARCH_NOKEY = empty
+    uint64_t* c_cnt;             // visits
+    uint64_t* c_sent;            // the part of c_cnt a delta pack does not send: sent before, or foreign
+    uint32_t* tgt;               // [npad] per env: its entry, or PK_ARCH_NONE
+    const uint64_t* keys;        // pk_counts_update: caller's arrays
+    const uint8_t* mask;
+    uint64_t* counts_out;
+    double* bonus_out;
+    const struct pk_crec* rec;   // pk_counts_add: caller's records, items [0, env1)
+    struct pk_crec* pack;        // pk_counts_pack: caller's records and their number
+    uint32_t* n_out;
+    uint64_t max_records;
+    uint64_t limit;              // distinct keys the table takes: 3/4 of its entries
+    double beta;
+    uint32_t c_mask;
+    uint32_t env0, env1;
+    uint32_t peek, foreign, delta;
+};

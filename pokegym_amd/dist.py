@@ -138,3 +138,23 @@ def archive_all_gather(records: torch.Tensor, payloads: torch.Tensor, rows: torc
             dist.all_gather(bufs, t, group=group)
         out.append(bufs)
     return out
+
+
+def counts_all_gather(records: torch.Tensor, n: torch.Tensor, group=None):
+    """all_gather of one rank's packed visit counts (BatchedEmulator.counts_pack_raw): the ranks
+    exchange their record counts first, then their int64 (k, 2) rows padded to the largest count.
+    Returns one tensor per rank, in rank order, cut to the rank's own count.  Reads the counts back."""
+    world = dist.get_world_size(group)
+    mine = n.reshape(1).to(torch.int64)
+    lens = [torch.empty_like(mine) for _ in range(world)]
+    dist.all_gather(lens, mine, group=group)
+    lens = [int(v) for v in lens]
+    k = max(lens)
+    if k == 0:
+        return [records[:0] for _ in range(world)]
+    own = lens[dist.get_rank(group)]
+    t = records.new_zeros((k, 2))       # the rows past this rank's own count travel as zeros
+    t[:own] = records[:own]
+    bufs = [torch.empty_like(t) for _ in range(world)]
+    dist.all_gather(bufs, t, group=group)
+    return [b[:m] for b, m in zip(bufs, lens)]

@@ -398,6 +398,83 @@ class BatchedEmulator:
                                        ctypes.c_void_p(out.data_ptr()), self._stream()), "pk_archive_merge")
         return out
 
+    # -- visit counts (stream-ordered except create / read; pack reads its length back) ----
+    # a packed key: pk_crec {key, count}, 16 bytes; records travel as int64 (k, 2) tensors (the 64 key
+    # bits as an int64, like every key tensor here)
+    def counts_create(self, cap_log2: int):
+        """Give the handle a visit-count table of 2**cap_log2 entries (pk_counts_create; once,
+        synchronous; any handle).  It takes counts_limit distinct keys."""
+        check(self._L.pk_counts_create(self._h, int(cap_log2)), "pk_counts_create")
+
+    @property
+    def counts_limit(self) -> int:
+        """Distinct keys the table takes, 3/4 of its entries; 0 without a table."""
+        return int(self._L.pk_counts_limit(self._h))
+
+    def counts_update(self, keys: torch.Tensor, mask: torch.Tensor | None = None, env0: int = 0, count: int | None = None,
+                      beta: float = 1.0, peek: bool = False, counts_out: torch.Tensor | None = None,
+                      bonus_out: torch.Tensor | None = None):
+        """Count the keys (int64: the 64 key bits; -1 is the reserved "no key") of the envs of the
+        range with mask[e] != 0 and return (counts_out, bonus_out): each env's key's new count (int64)
+        and beta / sqrt(count) (float64), 0 for envs that take no part or find the table full
+        (pk_counts_update, on the current stream; full-size tensors, the rest of the outputs is
+        untouched).  peek=True counts nothing and returns the stored counts."""
+        count = self.n - env0 if count is None else count
+        if counts_out is None:
+            counts_out = torch.zeros(self.n, dtype=torch.int64, device=self.device)
+        if bonus_out is None:
+            bonus_out = torch.zeros(self.n, dtype=torch.float64, device=self.device)
+        check(self._L.pk_counts_update(self._h, self._full(keys, torch.int64, "keys"), self._full(mask, torch.uint8, "mask"),
+                                       env0, count, float(beta), _native.PK_COUNTS_PEEK if peek else 0,
+                                       self._full(counts_out, torch.int64, "counts_out"),
+                                       self._full(bonus_out, torch.float64, "bonus_out"), self._stream()), "pk_counts_update")
+        return counts_out, bonus_out
+
+    def _crecs(self, records: torch.Tensor):
+        if records.dtype != torch.int64 or records.device != self.device or records.dim() != 2 \
+                or records.shape[1] != 2 or not records.is_contiguous() or records.data_ptr() % 16:
+            raise ValueError("records must be a contiguous, 16-byte aligned int64 (k, 2) tensor on the emulator's device")
+        return ctypes.c_void_p(records.data_ptr())
+
+    def counts_add(self, records: torch.Tensor, foreign: bool = False):
+        """Add packed counts, int64 (k, 2) rows of key and count, to the table (pk_counts_add, on the
+        current stream).  foreign=True: they came from another handle and are never sent on by a
+        delta pack of this one."""
+        p = self._crecs(records)
+        if records.shape[0]:
+            check(self._L.pk_counts_add(self._h, p, int(records.shape[0]), _native.PK_COUNTS_FOREIGN if foreign else 0,
+                                        self._stream()), "pk_counts_add")
+
+    def counts_pack_raw(self, delta: bool = False):
+        """(records, n): an int64 (counts_limit, 2) tensor whose first n rows (n an int32 scalar tensor)
+        are the packed keys, in no order (pk_counts_pack, on the current stream; no host sync)."""
+        limit = self.counts_limit
+        records = torch.empty((max(limit, 1), 2), dtype=torch.int64, device=self.device)
+        n = torch.zeros((), dtype=torch.int32, device=self.device)
+        check(self._L.pk_counts_pack(self._h, _native.PK_COUNTS_DELTA if delta else 0, self._crecs(records), limit,
+                                     ctypes.c_void_p(n.data_ptr()), self._stream()), "pk_counts_pack")
+        return records, n
+
+    def counts_pack(self, delta: bool = False) -> torch.Tensor:
+        """The table as int64 (k, 2) device rows of key and count, sorted by key as an unsigned number:
+        every stored key, or with delta=True what this handle counted itself since its last delta
+        pack (the keys it counted nothing for are left out).  Reads k back (a host sync)."""
+        records, n = self.counts_pack_raw(delta)
+        records = records[:int(n)]
+        order = torch.argsort(records[:, 0] ^ torch.iinfo(torch.int64).min)
+        return records[order].contiguous()
+
+    def counts_read(self) -> dict:
+        """{"used": distinct keys stored, "overflow": keys a full table turned away} (pk_counts_read;
+        synchronous)."""
+        used, overflow = ctypes.c_uint64(), ctypes.c_uint64()
+        check(self._L.pk_counts_read(self._h, ctypes.byref(used), ctypes.byref(overflow)), "pk_counts_read")
+        return {"used": int(used.value), "overflow": int(overflow.value)}
+
+    def counts_clear(self):
+        """Empty the table (pk_counts_clear, on the current stream)."""
+        check(self._L.pk_counts_clear(self._h, self._stream()), "pk_counts_clear")
+
     # -- action trajectories (stream-ordered except enable) -------------------------------
     def traj_enable(self):
         """Record every env's actions from here on (pk_traj_enable; once, synchronous).  Call it

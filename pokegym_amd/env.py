@@ -51,6 +51,23 @@ def _read(path_or_bytes):
         return f.read()
 
 
+def _key_args(what: str, key, frame, render: bool):
+    """Validate a key choice ("ram", "frame" or "frame+ram") and its (bw, bh, levels); what = the
+    argument prefix, "archive" or "novelty"."""
+    if key not in ("ram", "frame", "frame+ram"):
+        raise ValueError(f'{what}_key must be "ram", "frame" or "frame+ram", not {key!r}')
+    try:
+        bw, bh, levels = (int(v) for v in frame)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}_frame must be (bw, bh, levels)") from None
+    if bw not in (8, 16, 32, 40, 80, 160) or bh not in (8, 16, 24, 48, 72, 144) or not 2 <= levels <= 256:
+        raise ValueError(f"{what}_frame = (bw, bh, levels): bw a multiple of 8 that divides 160, bh one that "
+                         "divides 144, levels in 2..256")
+    if key != "ram" and not render:
+        raise ValueError(f'{what}_key="{key}" reads the screen: the emulator needs render=True')
+    return key, (bw, bh, levels)
+
+
 def _seen_cap_log2(max_episode_steps: int) -> int:
     """log2 of the seen-coordinate set's capacity for an episode length (pk_create /
     pk_set_episode_params: one entry per step at most, load factor <= 3/4, at least 1024)."""
@@ -247,7 +264,8 @@ class VecEnv:
                  state_pool=None, pool_seed: int = 0, bank_slots: int = 0, bank_episodes: bool = False,
                  fork_slots: int = 0, archive_cells: int = 0, archive_seed: int = 0, archive_shift: int = 0,
                  record_trajectories: bool = False, archive_exchange: bool = False, archive_key: str = "ram",
-                 archive_frame=(16, 16, 8)):
+                 archive_frame=(16, 16, 8), novelty_log2: int = 0, novelty_beta: float = 1.0, novelty_key: str = "frame",
+                 novelty_frame=(16, 16, 8)):
         """reward=False: the screen-obs env of configs[3] — obs is the (144, 160) u8 screen, rewards are
         0 and episodes end at max_episode_steps.  power_on=True starts (and resets) every env from
         the cartridge's power-on state instead of a savestate.
@@ -287,7 +305,19 @@ class VecEnv:
         archive_trajectory(cell), return the action list that reaches a state and the slot it starts
         from — a demonstration, and with BatchedEmulator.replay() the way to rebuild a slot or a
         whole archive after a restart.  Checkpoints, resumes, forks and the archive carry the lists
-        along.  Without it nothing is allocated or launched."""
+        along.  Without it nothing is allocated or launched.
+
+        novelty_log2=L (10..30; 0 = off) adds a count-based exploration bonus on any cartridge, with or
+        without the reward stack: a device table of 2**L entries (pk_counts_*) counts the key of the
+        frame every step ends on — the last frame of an episode counts, the frame an auto-reset
+        restarts from never does — and the returned rewards are the extrinsic reward plus
+        novelty_beta / sqrt(visits of the key, this one included); with reward=False they are the bonus
+        alone.  The episode statistics keep the extrinsic return.  novelty_key and novelty_frame
+        choose the key as archive_key and archive_frame do (the "ram" key uses archive_shift).  Each
+        sub-batch takes its keys on its own stream right after its step; the table, one shared
+        structure, is updated where calls are in one order: inside step() in batch order, and in the
+        recv() that returns a sub-batch.  novelty_keys / novelty_counts / novelty_bonus are the last
+        values per env; counts_sync() adds up the tables of a torch.distributed group."""
         self.batch_size = batch_size or num_envs
         if num_envs % self.batch_size:
             raise ValueError("batch_size must divide num_envs")
@@ -360,18 +390,22 @@ class VecEnv:
         if self.fork_slots and not bank_episodes:
             raise ValueError("fork_slots needs bank_episodes=True")
         self.archive_cells, self.archive_shift = int(archive_cells), int(archive_shift)
-        if archive_key not in ("ram", "frame", "frame+ram"):
-            raise ValueError(f'archive_key must be "ram", "frame" or "frame+ram", not {archive_key!r}')
-        try:
-            bw, bh, levels = (int(v) for v in archive_frame)
-        except (TypeError, ValueError):
-            raise ValueError("archive_frame must be (bw, bh, levels)") from None
-        if bw not in (8, 16, 32, 40, 80, 160) or bh not in (8, 16, 24, 48, 72, 144) or not 2 <= levels <= 256:
-            raise ValueError("archive_frame = (bw, bh, levels): bw a multiple of 8 that divides 160, bh one that "
-                             "divides 144, levels in 2..256")
-        if archive_key != "ram" and not getattr(emulator, "render", True):
-            raise ValueError(f'archive_key="{archive_key}" reads the screen: the emulator needs render=True')
-        self.archive_key, self.archive_frame = archive_key, (bw, bh, levels)
+        self.archive_key, self.archive_frame = _key_args("archive", archive_key, archive_frame,
+                                                         getattr(emulator, "render", True))
+        # count-based novelty bonus (pk_counts_*): nothing is allocated or called with novelty_log2 = 0
+        self.novelty_log2, self.novelty_beta = int(novelty_log2), float(novelty_beta)
+        self.novelty_key, self.novelty_frame = _key_args("novelty", novelty_key, novelty_frame,
+                                                         not self.novelty_log2 or getattr(emulator, "render", True))
+        self._nov_keys = self._nov_counts = self._nov_bonus = None
+        # per sub-batch of the pipeline: 0 = nothing owed, 1 = sent, its keys not counted yet (recv()
+        # counts them), 2 = counted by a flush, recv() still owes its bonus to the returned rewards
+        self._nov_due = [0] * self.num_batches
+        if self.novelty_log2:
+            self.emu.counts_create(self.novelty_log2)
+            # emulator order; padding envs keep key -1 ("no key") and never count
+            self._nov_keys = torch.full((n_phys,), -1, dtype=torch.int64, device=self.device)
+            self._nov_counts = torch.zeros(n_phys, dtype=torch.int64, device=self.device)
+            self._nov_bonus = torch.zeros(n_phys, dtype=torch.float64, device=self.device)
         self._arch0 = 0             # first slot of the archive's cells
         self._arch_out = None
         self.archive_exchange = bool(archive_exchange)
@@ -807,8 +841,79 @@ class VecEnv:
             raise ERR_EXCEPTIONS.get(code, RuntimeError)(
                 f"env {e}: reference reward stack raises here (PK_ERR {code}); {bad.numel()} env(s) failed")
 
-    def _step_range(self, b: int, actions: torch.Tensor):
-        """Step sub-batch b (envs _range(b)) on the current stream, then book-keep and auto-reset."""
+    def _novelty_take(self, psl: slice):
+        """The keys of emulator envs psl into _nov_keys, on the current stream; no table is touched."""
+        env0, count = psl.start, psl.stop - psl.start
+        if self.novelty_key == "ram":
+            self.emu.cell_keys(self.archive_shift, out=self._nov_keys, env0=env0, count=count)
+            return
+        salt = None
+        if self.novelty_key == "frame+ram":
+            salt = self.emu.cell_keys(self.archive_shift, out=self._nov_keys, env0=env0, count=count)
+        self.emu.frame_keys(*self.novelty_frame, salt=salt, out=self._nov_keys, env0=env0, count=count)
+
+    def _novelty_count(self, psl: slice) -> torch.Tensor:
+        """Count the keys taken for emulator envs psl (one table update, on the current stream);
+        returns their bonus."""
+        self.emu.counts_update(self._nov_keys, None, psl.start, psl.stop - psl.start, self.novelty_beta, False,
+                               self._nov_counts, self._nov_bonus)
+        return self._nov_bonus[psl]
+
+    def _novelty_flush(self):
+        """Count the sub-batches that were sent and not received yet, in batch order (the streams are
+        joined).  Their bonus stays in _nov_bonus, which only the sub-batch's next count overwrites;
+        the recv() that returns such a sub-batch adds it to the rewards."""
+        for b, due in enumerate(self._nov_due):
+            if due == 1:
+                self._nov_due[b] = 2
+                self._novelty_count(self._prange(b))
+
+    def _novelty_last(self, t):
+        if t is None:
+            raise RuntimeError("VecEnv(novelty_log2=...) counts visits")
+        self._join_streams()
+        return self._logical(t).clone()
+
+    @property
+    def novelty_keys(self) -> torch.Tensor:
+        """The key every env's last step ended on (int64, env order; -1 before the first step)."""
+        return self._novelty_last(self._nov_keys)
+
+    @property
+    def novelty_counts(self) -> torch.Tensor:
+        """The visits of that key when the step was counted, itself included (int64, env order)."""
+        return self._novelty_last(self._nov_counts)
+
+    @property
+    def novelty_bonus(self) -> torch.Tensor:
+        """novelty_beta / sqrt(novelty_counts): the part of the last returned reward that is the bonus."""
+        return self._novelty_last(self._nov_bonus)
+
+    def counts_sync(self, group=None):
+        """Add up the visit counts of the ranks of a torch.distributed group: a delta pack (what this
+        rank counted itself since the last call), an all_gather of the records, then every other
+        rank's records added in ascending rank order, as counts that are never sent on.  A
+        collective: every rank calls it.  World size 1 (or no process group) is a no-op.  On the
+        current stream after a pipeline join; reads the ranks' record counts back (a host sync).
+        In a recv() / send() loop the sub-batches that are sent and not received yet are counted
+        here, so that they travel with this call; their recv() returns the bonus all the same."""
+        from .dist import counts_all_gather
+        if not self.novelty_log2:
+            raise RuntimeError("VecEnv(novelty_log2=...) counts visits")
+        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+            return
+        self._join_streams()
+        self._novelty_flush()
+        records, n = self.emu.counts_pack_raw(delta=True)
+        me = dist.get_rank(group)
+        for r, rec in enumerate(counts_all_gather(records, n, group)):
+            if r != me:
+                self.emu.counts_add(rec, foreign=True)
+
+    def _step_range(self, b: int, actions: torch.Tensor, count_now: bool = False):
+        """Step sub-batch b (envs _range(b)) on the current stream, then book-keep and auto-reset.
+        With the novelty bonus the step's keys are taken here; count_now also counts them (step():
+        one stream, batch order), else recv() does."""
         sl, psl = self._range(b), self._prange(b)
         if self.num_batches == 1:
             obs, rew, term, trunc = self.emu.step(actions)
@@ -821,6 +926,13 @@ class VecEnv:
             se = self.sticky_errors[psl]
             torch.where(se != 0, se, self.emu.errors[psl], out=se)
         rewards = rew.clone()
+        if self.novelty_log2:       # the frame the step ended on, before an auto-reset replaces it
+            self._novelty_take(psl)
+            if count_now:
+                rewards += self._novelty_count(psl)
+                self._nov_due[b] = 0
+            else:
+                self._nov_due[b] = 1
         terminals = term.to(torch.bool)
         truncations = trunc.to(torch.bool)
         # auto-reset the finished envs (no host sync); their obs is the first obs of the next episode
@@ -892,10 +1004,12 @@ class VecEnv:
         if self._log_wait:
             self._log_wait = 0
             pending = self._read_logs()
+        if self.novelty_log2:
+            self._novelty_flush()
         if self.num_batches == 1:
-            obs, rewards, terminals, truncations = self._step_range(0, a)
+            obs, rewards, terminals, truncations = self._step_range(0, a, True)
         else:
-            outs = [self._step_range(b, a[self._range(b)]) for b in range(self.num_batches)]
+            outs = [self._step_range(b, a[self._range(b)], True) for b in range(self.num_batches)]
             obs = self._logical(self.emu.obs if self.emu.reward else self.emu.screen)
             rewards = torch.cat([o[1] for o in outs])
             terminals = torch.cat([o[2] for o in outs])
@@ -945,6 +1059,7 @@ class VecEnv:
             self._events[b].record(cur)
         self._ready = list(range(self.num_batches))
         self._current = None
+        self._nov_due = [0] * self.num_batches
 
     def recv(self):
         """The next finished sub-batch: (obs, rewards, terminals, truncations, infos, env_ids, masks),
@@ -970,6 +1085,10 @@ class VecEnv:
         self._current = b
         sl = self._range(b)
         rew, term, trunc = self._pending[b]
+        if self._nov_due[b]:        # the table is updated here, on the consumer's stream, in recv() order
+            psl = self._prange(b)   # (a counts_sync() in between has counted the sub-batch already)
+            rew = rew + (self._novelty_count(psl) if self._nov_due[b] == 1 else self._nov_bonus[psl])
+            self._nov_due[b] = 0
         obs = self.emu.obs if self.emu.reward else self.emu.screen
         infos, self._pending_infos = getattr(self, "_pending_infos", []) + logged, []
         return obs[self._prange(b)], rew, term, trunc, infos, self.env_ids[sl], self.masks[sl]
