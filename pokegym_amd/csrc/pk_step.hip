@@ -1273,7 +1273,7 @@ __global__ void __launch_bounds__(PK_K1_MAX_THREADS) PK_K1_KERNEL(PkStepArgs A) 
             // the misc word; never for the other entries and when not fused)
             const bool tk2 = (((s.w1 & u2.x) ^ M2) & 0x00FF0000u) == 0u;
             const u32 pc2 = (s.pc + (M2 & 3u) + sel(tk2, (u32)sfield(nxt, 8, 8), 0u)) & 0xFFFFu;
-            if (fuse) PK_TRACE(env, s.pc, s.w0, perm(s.w1, s.w1, 0x02030100u), s.sp, nxt & 0xFFu);
+            if (fuse) PK_TRACE(env, s.pc, s.w0, perm(s.w1, s.w1, 0x02030100u), s.sp, (nxt & 0xFFu) | 0x2000u);
             ev |= sel(fuse, PK_EV_FUSE, 0u);
 #ifdef PK_DBG_FUSE
             ev |= sel(len2 != 0u, 1u << 23, 0u) | sel((int)cycles < slack, 1u << 24, 0u) | sel(s.clock + cycles < s.lim, 1u << 25, 0u)

@@ -130,7 +130,8 @@ void pk_sim_launch(const char* name, dim3 grid, dim3 block, const std::function<
 #define hipLaunchKernelGGL(k, grid, block, shmem, stream, ...) \
     pk_sim_launch(#k, dim3(grid), dim3(block), [&]() { k(__VA_ARGS__); })
 
-// instruction trace for debugging (env, pc, w0, w1, sp, opcode)
+// instruction trace for debugging (env, pc, w0, w1, sp, opcode; opcode | 0x2000: the instruction ran
+// as a fused secondary op)
 extern "C" void pk_sim_trace(uint32_t env, uint32_t pc, uint32_t w0, uint32_t w1, uint32_t sp, uint32_t op);
 #define PK_TRACE(env, pc, w0, w1, sp, op) pk_sim_trace(env, pc, w0, w1, sp, op)
 // loop fast-path marker: op = 0x1000 | loop length, w0 = passes run (tools/trace_diff.py)

@@ -70,7 +70,24 @@ extern "C" void pk_sim_trace_enable(uint32_t env, uint64_t cap) {
     g_trace_env = env;
     g_trace_cap = cap;
 }
+// opcode census over every env (tests/test_sm83_matrix.py): per pc, how many records of the primary
+// path ([0]) and of the fused secondary path ([1]: op bit 0x2000) ran there, and the last opcode
+static std::atomic<uint32_t>* g_census = nullptr;   // [2][65536] counts, then [2][65536] opcodes
+extern "C" void pk_sim_census_enable(int on) {
+    std::lock_guard<std::mutex> l(g_trace_mu);
+    delete[] g_census;
+    g_census = on ? new std::atomic<uint32_t>[4 * 65536]() : nullptr;
+}
+extern "C" void pk_sim_census_get(uint32_t* out /* 4 * 65536 */) {
+    std::lock_guard<std::mutex> l(g_trace_mu);
+    for (size_t i = 0; g_census && i < 4 * 65536; i++) out[i] = g_census[i].load();
+}
 extern "C" void pk_sim_trace(uint32_t env, uint32_t pc, uint32_t w0, uint32_t w1, uint32_t sp, uint32_t op) {
+    if (g_census && !(op & 0x1000u)) {
+        const size_t i = ((op >> 13) & 1u) * 65536u + (pc & 0xFFFFu);
+        g_census[i].fetch_add(1u);
+        g_census[2 * 65536 + i].store(op & 0xFFu);
+    }
     if (env != g_trace_env) return;
     std::lock_guard<std::mutex> l(g_trace_mu);
     if (g_trace.size() / 6 >= g_trace_cap) return;

@@ -421,6 +421,40 @@ def test_sm83_kat_on_device(small, monkeypatch):
     assert not bad, bad[:8]
 
 
+@pytest.mark.parametrize("small,n_banks", [(False, 2), (True, 2), (False, 64)])
+def test_sm83_matrix_on_device(small, n_banks, monkeypatch):
+    """The HIP K1 runs the opcode-matrix ROM (pokegym_amd/testrom/kat_matrix.py): every legal opcode
+    but HALT / STOP / DI / EI in a block behind a taken jp (K1's primary table entry) and, for the
+    opcodes of the secondary table, in a block behind a nop (the fused path), each over V vectors of
+    registers, flags and memory; one group of blocks per env (64 envs).  Every block hash == the
+    documented CPU's (tests/sm83_spec.py step()), wDone set, and the whole state == the oracle's; in
+    the default kernel (2 banks, and 64: half of the blocks fetched from the global ROM) and in the
+    small-LDS kernel of the VecEnv sub-batches."""
+    import torch
+    from pokegym_amd.emulator import BatchedEmulator
+    from pokegym_amd.testrom import kat_matrix as KM
+    from tests.test_sm83_matrix import check_groups, kernel_block_hashes, matrix
+    if small:
+        monkeypatch.setenv("PK_K1_SMALL", "1")
+        monkeypatch.setenv("PK_WAVE_LANES", "32")
+        monkeypatch.setenv("PK_K1_BLOCK", "256")
+    n, steps = 64, 8
+    m = matrix(n_banks)
+    groups = [e % 8 for e in range(n)]
+    acts = np.array([KM.GROUP_ACTION[g] for g in groups], np.uint8)
+    emu = BatchedEmulator(m.rom, n, render=True)
+    a = torch.from_numpy(acts).to(emu.device)
+    for _ in range(steps):
+        emu.step(a)
+    torch.cuda.synchronize()
+    states = emu.snapshot_range(0, n)
+    emu.close()
+    assert check_groups(m, kernel_block_hashes(m, states), groups) == []
+    ref, _ = oracle.batch_run(m.rom, None, np.repeat(acts[None, :], steps, axis=0), want_screens=False)
+    bad = [e for e in range(n) if states[e].tobytes() != ref[e].tobytes()]
+    assert not bad, bad[:8]
+
+
 # ---------------------------------------------------------------------------------------------
 # Every step end, not only the last: per-frame parity (frame_skip=1) and the other values of
 # frame_skip / release_frame, the two pk_config fields the tests above never vary.
