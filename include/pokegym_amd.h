@@ -589,6 +589,57 @@ int pk_counts_pack(pk_handle* h, uint32_t flags, pk_crec* rec_dev, uint64_t max_
 int pk_counts_read(pk_handle* h, uint64_t* used, uint64_t* overflow);
 int pk_counts_clear(pk_handle* h, void* stream);
 
+/* Frame stack: a downscaled, k-deep frame history per env, kept on the device and updated in place
+ * by one launch per step — the observation of a pixel policy on any cartridge (the reference's
+ * screen[::2, ::2] and its 3-deep recent_frames, newest first).  It needs nothing else: no
+ * PK_F_REWARD, no bank.
+ *
+ * Geometry: scale s is 1, 2 or 4, a plane is H x W = (144 / s) x (160 / s) bytes (scale 8 is left
+ * out: an 18 x 20 plane is no multiple of 16 bytes).  depth D is 1..8 with PK_FSTACK_CHW, u8[n][D][H][W],
+ * and 1, 2, 4 or 8 with PK_FSTACK_HWC, u8[n][H][W][D].  Plane 0 is always the newest.  The stack takes
+ * n * D * H * W bytes: 23,040 per env at s = 2, D = 4, 1.5 GB at 65,536 envs.  HWC at s = 2, D = 4 has
+ * the reference observation's shape (72, 80, 4); CHW at s = 4, D = 3 is its 3 x 36 x 40 screen stack.
+ *
+ * The plane p of a screen, for any byte values, in integers:
+ *   PK_FSTACK_MEAN   p[y][x] = (sum over dy, dx < s of screen[s*y + dy][s*x + dx] + s*s/2) div (s*s)
+ *   PK_FSTACK_PICK   p[y][x] = screen[s*y][s*x]
+ * With s = 1 both are the screen.
+ *
+ * pk_fstack_create (synchronous): once per handle, on any handle; the stack starts as all zeros.  On
+ * failure (second call, bad argument, out of memory) the handle is unchanged.  pk_fstack_depth and
+ * pk_fstack_scale are 0 and pk_fstack_ptr is NULL without a stack, and pk_fstack_push then fails with
+ * a negative code.  A handle that never creates one makes exactly the launches and allocations it
+ * made before.  pk_fstack_ptr is a device pointer the handle owns, valid until pk_destroy.
+ *
+ * pk_fstack_push (one launch, stream-ordered, no host sync, no allocation): screen_dev NULL is the
+ * handle's own screen (needs PK_F_RENDER, the call fails without it), otherwise a caller's device
+ * u8[n][144][160], 16-byte aligned — pk_frame_keys' rules.  mask_dev is NULL or a full-size device
+ * u8[n]; the range follows pk_step_range's rule.
+ *   flags == 0: every env of the range takes part.  With mask[e] != 0 the env FILLS: all D planes
+ *     become the new plane.  Otherwise (a NULL mask included) it PUSHES: plane k becomes the old
+ *     plane k - 1 for k = D - 1 .. 1 and plane 0 the new plane.
+ *   PK_FSTACK_FILL_ONLY: only the envs with mask[e] != 0 take part (a NULL mask: every env of the
+ *     range), and they fill; the other envs keep every byte.
+ * Nothing outside the rows of [env0, env0 + count) is written, so disjoint ranges may run
+ * concurrently on different streams.  Bad arguments (no stack, unknown flag bits, a misaligned
+ * screen pointer, a range past n, an env0 that is no multiple of 64) are a negative code with
+ * pk_last_error, never a fault, and write nothing.
+ *
+ * A stack belongs to the env, not to the episode or the machine: bank slots, checkpoints, the
+ * archive and the exchange payload do not carry it and keep their formats.  The caller refills
+ * (PK_FSTACK_FILL_ONLY) an env whose machine was replaced; VecEnv(frame_stack=D) does. */
+#define PK_FSTACK_CHW 0u        /* u8[n][depth][H][W] */
+#define PK_FSTACK_HWC 1u        /* u8[n][H][W][depth] */
+#define PK_FSTACK_MEAN 0u
+#define PK_FSTACK_PICK 1u
+#define PK_FSTACK_FILL_ONLY 1u  /* pk_fstack_push flag */
+int pk_fstack_create(pk_handle* h, uint32_t scale, uint32_t depth, uint32_t layout, uint32_t mode);
+uint32_t pk_fstack_depth(const pk_handle* h);       /* 0 without a stack */
+uint32_t pk_fstack_scale(const pk_handle* h);       /* 0 without a stack */
+uint8_t* pk_fstack_ptr(pk_handle* h);               /* device pointer, owned by the handle; NULL without */
+int pk_fstack_push(pk_handle* h, const uint8_t* screen_dev, const uint8_t* mask_dev, uint32_t flags,
+                   uint32_t env0, uint32_t count, void* stream);
+
 /* Emulated instructions executed by the last pk_step, summed over envs (synchronous). */
 int pk_last_instr_count(pk_handle* h, uint64_t* out);
 

@@ -24,6 +24,9 @@ PK_XCHG_DELTA = 1
 PK_COUNTS_PEEK = 1
 PK_COUNTS_FOREIGN = 1
 PK_COUNTS_DELTA = 1
+PK_FSTACK_CHW, PK_FSTACK_HWC = 0, 1
+PK_FSTACK_MEAN, PK_FSTACK_PICK = 0, 1
+PK_FSTACK_FILL_ONLY = 1
 HEAT_SHAPE = (444, 436)
 OBS_SHAPE = (72, 80, 4)
 # PK_ERR_* -> the exception the reference raises at that point (include/pokegym_amd.h)
@@ -49,7 +52,8 @@ EXPORTS = ("pk_create", "pk_destroy", "pk_last_error", "pk_abi_version", "pk_res
            "pk_archive_merge",
            "pk_frame_cells", "pk_frame_keys",
            "pk_counts_create", "pk_counts_limit", "pk_counts_update", "pk_counts_add", "pk_counts_pack",
-           "pk_counts_read", "pk_counts_clear")
+           "pk_counts_read", "pk_counts_clear",
+           "pk_fstack_create", "pk_fstack_depth", "pk_fstack_scale", "pk_fstack_ptr", "pk_fstack_push")
 
 
 class PkConfig(ctypes.Structure):
@@ -137,6 +141,7 @@ def bind(L):
     bind_v11(L)
     bind_v12(L)
     bind_counts(L)
+    bind_fstack(L)
 
 
 def bind_v2(L):
@@ -249,6 +254,20 @@ def bind_counts(L):
     L.pk_counts_pack.argtypes = [vp, u32, vp, u64, vp, vp]
     L.pk_counts_read.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
     L.pk_counts_clear.argtypes = [vp, vp]
+
+
+def bind_fstack(L):
+    """argtypes of the frame stack (additive to ABI v12; shared with the host-simulation test build)."""
+    vp = ctypes.c_void_p
+    u32 = ctypes.c_uint32
+    L.pk_fstack_create.argtypes = [vp, u32, u32, u32, u32]
+    L.pk_fstack_depth.argtypes = [vp]
+    L.pk_fstack_depth.restype = u32
+    L.pk_fstack_scale.argtypes = [vp]
+    L.pk_fstack_scale.restype = u32
+    L.pk_fstack_ptr.argtypes = [vp]
+    L.pk_fstack_ptr.restype = vp
+    L.pk_fstack_push.argtypes = [vp, vp, vp, u32, u32, u32, vp]
 
 
 def check(rc: int, what: str):

@@ -51,6 +51,7 @@ hipError_t pk_launch_arch_out(const PkArchArgs& a, hipStream_t s);
 hipError_t pk_launch_cell_keys(const uint8_t* mem, uint32_t sh, uint32_t shift, uint64_t* keys, uint32_t env0,
                                uint32_t env1, hipStream_t s);
 hipError_t pk_launch_frame_keys(const PkCellArgs& a, hipStream_t s);
+hipError_t pk_launch_fstack(const PkStackArgs& a, hipStream_t s);
 hipError_t pk_launch_cnt_update(const PkCountArgs& a, hipStream_t s);
 hipError_t pk_launch_cnt_add(const PkCountArgs& a, hipStream_t s);
 hipError_t pk_launch_cnt_pack(const PkCountArgs& a, hipStream_t s);
@@ -335,6 +336,9 @@ struct pk_handle {
     // header words, the three arrays of the table and the per-env entry words of an update
     uint32_t cnt_log2 = 0;
     uint8_t* c_fix = nullptr;
+    // frame stack (pk_fstack_create; pk_layout.h PkStackArgs), fs_depth = 0 without one: u8[n][D * H * W]
+    uint32_t fs_scale = 0, fs_depth = 0, fs_layout = 0, fs_mode = 0;
+    uint8_t* fs_stack = nullptr;
     // profiling: 4 events per profiled step (start, after K1, after K2, after K4+K3)
     bool prof = false;
     std::vector<hipEvent_t> ev_pool;
@@ -377,7 +381,7 @@ void pk_destroy(pk_handle* h) {
                     h->b_mem, h->b_regs, h->b_lat, h->b_screen, h->b_filled, h->b_rejects, h->b_lists, h->b_src,
                     h->e_fields, h->e_seen, h->e_mask, h->e_cutc, h->b_ep_filled, h->a_fix, h->a_ones, h->a_zero,
                     h->x_fix, h->x_ones, h->x_zero, h->t_act, h->t_origin, h->t_flags, h->bt_act, h->bt_origin, h->bt_flags,
-                    h->c_fix};
+                    h->c_fix, h->fs_stack};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     delete h;
@@ -1645,6 +1649,55 @@ int pk_frame_keys(pk_handle* h, uint32_t bw, uint32_t bh, uint32_t levels, const
     a.screen = screen ? screen : h->screen; a.salt = salt; a.keys = keys; a.cells = cells;
     a.env0 = env0; a.env1 = env0 + count; a.bw = bw; a.bh = bh; a.levels = levels;
     HIPCHK(pk_launch_frame_keys(a, (hipStream_t)stream));
+    return 0;
+}
+
+// ---- frame stack --------------------------------------------------------------------------------
+
+uint32_t pk_fstack_depth(const pk_handle* h) { return h ? h->fs_depth : 0; }
+uint32_t pk_fstack_scale(const pk_handle* h) { return h && h->fs_depth ? h->fs_scale : 0; }
+uint8_t* pk_fstack_ptr(pk_handle* h) { return h ? h->fs_stack : nullptr; }
+
+int pk_fstack_create(pk_handle* h, uint32_t scale, uint32_t depth, uint32_t layout, uint32_t mode) {
+    if (!h) return fail(-EINVAL, "null handle");
+    if (h->fs_depth) return fail(-EEXIST, "the handle already has a frame stack of depth %u", h->fs_depth);
+    if (scale != 1 && scale != 2 && scale != 4) return fail(-EINVAL, "scale must be 1, 2 or 4");
+    if (layout != PK_FSTACK_CHW && layout != PK_FSTACK_HWC) return fail(-EINVAL, "unknown layout %u", layout);
+    if (mode != PK_FSTACK_MEAN && mode != PK_FSTACK_PICK) return fail(-EINVAL, "unknown mode %u", mode);
+    if (depth == 0 || depth > PK_FS_MAX_DEPTH) return fail(-EINVAL, "depth must be 1..%u", PK_FS_MAX_DEPTH);
+    if (layout == PK_FSTACK_HWC && (depth & (depth - 1u))) return fail(-EINVAL, "depth must be 1, 2, 4 or 8 with PK_FSTACK_HWC");
+    HIPCHK(hipSetDevice(h->device));
+    const size_t bytes = (size_t)h->n * depth * (PK_SCREEN / (scale * scale));
+    uint8_t* p = nullptr;
+    hipError_t e = hipMalloc((void**)&p, bytes);
+    if (e == hipSuccess) e = hipMemset(p, 0, bytes);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        if (p) (void)hipFree(p);
+        (void)hipGetLastError();
+        return fail(-ENOMEM, "frame stack of depth %u at scale %u (%zu bytes): %s", depth, scale, bytes, hipGetErrorString(e));
+    }
+    h->fs_stack = p;
+    h->fs_scale = scale; h->fs_depth = depth; h->fs_layout = layout; h->fs_mode = mode;
+    return 0;
+}
+
+int pk_fstack_push(pk_handle* h, const uint8_t* screen, const uint8_t* mask, uint32_t flags, uint32_t env0, uint32_t count,
+                   void* stream) {
+    int rc;
+    if ((rc = check_range(h, env0, count))) return rc;
+    if (!h->fs_depth) return fail(-ENOENT, "the handle has no frame stack (pk_fstack_create)");
+    if (flags & ~PK_FSTACK_FILL_ONLY) return fail(-EINVAL, "unknown flags 0x%x", flags);
+    if (!screen && !(h->flags & PK_F_RENDER))
+        return fail(-ENOTSUP, "the handle renders no screen (PK_F_RENDER): pass screen_dev");
+    if ((uintptr_t)screen % 16u) return fail(-EINVAL, "screen_dev must be 16-byte aligned");
+    HIPCHK(hipSetDevice(h->device));
+    PkStackArgs a;
+    a.screen = screen ? screen : h->screen; a.mask = mask; a.stack = h->fs_stack;
+    a.env0 = env0; a.env1 = env0 + count;
+    a.scale = h->fs_scale; a.depth = h->fs_depth; a.layout = h->fs_layout; a.mode = h->fs_mode;
+    a.fill_only = flags & PK_FSTACK_FILL_ONLY;
+    HIPCHK(pk_launch_fstack(a, (hipStream_t)stream));
     return 0;
 }
 

@@ -919,6 +919,157 @@ hipError_t pk_launch_frame_keys(const PkCellArgs& a, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Frame stack (pk_fstack_push): the downscaled screen pushed onto, or filled into, every env's stack
+// of D planes, in place (include/pokegym_amd.h states the model).  thread = one piece of PX
+// consecutive output pixels of one row: it reads the S x S source pixels of each from the screen and
+// the older bytes of the same pixels from the stack into registers, then writes.  No thread reads
+// what another writes, so there is no barrier and no second buffer.  A workgroup is one wave and
+// works on one env (the mask byte is wave-uniform); consecutive lanes take consecutive pieces, so a
+// wave's loads and stores are consecutive 16-byte (8-byte at S = 4 in CHW) pieces of a plane.
+//   CHW  PX = 16 (S = 1, 2) or 8 (S = 4): D - 1 pieces read, D written, one per plane.
+//   HWC  PX = 16 / D: the D bytes of the PX pixels are one 16-byte piece, a pixel's bytes newest
+//        first, so a push is a shift by one byte: (old << 8) | new on a dword at D = 4.
+#ifndef PK_FS_WG
+#define PK_FS_WG 64u
+#endif
+
+template <u32 B> __device__ __forceinline__ void pk_fs_ld(const u8* p, u32* w) {
+    if constexpr (B == 32u) {
+        pk_fs_ld<16u>(p, w);
+        pk_fs_ld<16u>(p + 16, w + 4);
+    } else if constexpr (B == 16u) {
+        const uint4 v = *reinterpret_cast<const uint4*>(p);
+        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+    } else if constexpr (B == 8u) {
+        const uint2 v = *reinterpret_cast<const uint2*>(p);
+        w[0] = v.x; w[1] = v.y;
+    } else if constexpr (B == 4u) {
+        w[0] = *reinterpret_cast<const u32*>(p);
+    } else {
+        w[0] = *reinterpret_cast<const uint16_t*>(p);
+    }
+}
+
+template <u32 B> __device__ __forceinline__ void pk_fs_st(u8* p, const u32* w) {
+    if constexpr (B == 16u) *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
+    else *reinterpret_cast<uint2*>(p) = make_uint2(w[0], w[1]);
+}
+
+__device__ __forceinline__ u32 pk_fs_byte(const u32* w, u32 j) { return (w[j >> 2] >> (8u * (j & 3u))) & 0xFFu; }
+
+// the PX new pixels of a piece, packed four to a word: the rounded mean of each S x S block, or its
+// top left pixel
+template <u32 S, u32 PX> __device__ __forceinline__ void pk_fs_plane(const u8* src, u32 pick, u32* nw) {
+    constexpr u32 B = S * PX, NB = (B + 3u) / 4u, NW = (PX + 3u) / 4u;
+    u32 w[S][NB];
+    pk_fs_ld<B>(src, w[0]);
+#pragma unroll
+    for (u32 dy = 1; dy < S; dy++) {
+#pragma unroll
+        for (u32 j = 0; j < NB; j++) w[dy][j] = 0;
+        if (!pick) pk_fs_ld<B>(src + dy * PK_COLS, w[dy]);
+    }
+#pragma unroll
+    for (u32 i = 0; i < NW; i++) nw[i] = 0;
+#pragma unroll
+    for (u32 i = 0; i < PX; i++) {
+        u32 sum = 0;
+#pragma unroll
+        for (u32 dy = 0; dy < S; dy++)
+#pragma unroll
+            for (u32 dx = 0; dx < S; dx++) sum += pk_fs_byte(w[dy], S * i + dx);
+        const u32 v = pick ? pk_fs_byte(w[0], S * i) : (sum + S * S / 2u) / (S * S);
+        nw[i >> 2] |= v << (8u * (i & 3u));
+    }
+}
+
+template <u32 S, u32 PX, bool HWC> __global__ void __launch_bounds__(PK_FS_WG) pk_fstack_kernel(PkStackArgs A) {
+    constexpr u32 H = PK_ROWS / S, W = PK_COLS / S, PPR = W / PX, P = H * PPR, NW = (PX + 3u) / 4u;
+    constexpr u32 BPE = (P + PK_FS_WG - 1u) / PK_FS_WG;
+    const u32 e = A.env0 + blockIdx.x / BPE, p = (blockIdx.x % BPE) * PK_FS_WG + threadIdx.x;
+    if (e >= A.env1 || p >= P) return;
+    const u32 m = A.mask ? A.mask[e] : 0u;
+    if (A.fill_only && A.mask && !m) return;
+    const bool fill = A.fill_only || m;
+    const u32 y = p / PPR, x0 = (p % PPR) * PX;
+    const u8* src = A.screen + (size_t)e * PK_SCREEN + (size_t)(S * y) * PK_COLS + S * x0;
+    u32 nw[NW];
+    if constexpr (!HWC) {
+        u8* dst = A.stack + (size_t)e * A.depth * (H * W) + (size_t)p * PX;
+        u32 old[PK_FS_MAX_DEPTH][NW];          // old[k]: what plane k takes
+        pk_fs_plane<S, PX>(src, A.mode, nw);   // its loads and the older pieces' are all issued before a store
+#pragma unroll
+        for (u32 k = 1; k < PK_FS_MAX_DEPTH; k++) {
+            if (k >= A.depth) continue;
+            if (fill) {
+#pragma unroll
+                for (u32 i = 0; i < NW; i++) old[k][i] = nw[i];
+            } else {
+                pk_fs_ld<PX>(dst + (size_t)(k - 1u) * (H * W), old[k]);
+            }
+        }
+        pk_fs_st<PX>(dst, nw);
+#pragma unroll
+        for (u32 k = 1; k < PK_FS_MAX_DEPTH; k++)
+            if (k < A.depth) pk_fs_st<PX>(dst + (size_t)k * (H * W), old[k]);
+    } else {
+        constexpr u32 D = 16u / PX;
+        u8* dst = A.stack + ((size_t)e * (H * W) + (size_t)p * PX) * D;
+        u32 o[4] = {0u, 0u, 0u, 0u}, r[4];
+        if (!fill) pk_fs_ld<16u>(dst, o);
+        pk_fs_plane<S, PX>(src, A.mode, nw);
+        if constexpr (D == 2u) {
+#pragma unroll
+            for (u32 j = 0; j < 4u; j++) {
+                const u32 nn = pk_fs_byte(nw, 2u * j) | pk_fs_byte(nw, 2u * j + 1u) << 16;
+                r[j] = fill ? nn * 0x0101u : (((o[j] << 8) & 0xFF00FF00u) | nn);
+            }
+        } else if constexpr (D == 4u) {
+#pragma unroll
+            for (u32 j = 0; j < 4u; j++) {
+                const u32 nn = pk_fs_byte(nw, j);
+                r[j] = fill ? nn * 0x01010101u : ((o[j] << 8) | nn);
+            }
+        } else {
+#pragma unroll
+            for (u32 j = 0; j < 2u; j++) {
+                const u32 nn = pk_fs_byte(nw, j);
+                r[2u * j] = fill ? nn * 0x01010101u : ((o[2u * j] << 8) | nn);
+                r[2u * j + 1u] = fill ? nn * 0x01010101u : ((o[2u * j + 1u] << 8) | (o[2u * j] >> 24));
+            }
+        }
+        pk_fs_st<16u>(dst, r);
+    }
+}
+
+template <u32 S, u32 PX, bool HWC> static hipError_t pk_fs_launch(const PkStackArgs& a, hipStream_t s) {
+    constexpr u32 P = (PK_ROWS / S) * (PK_COLS / S / PX), BPE = (P + PK_FS_WG - 1u) / PK_FS_WG;
+    hipLaunchKernelGGL((pk_fstack_kernel<S, PX, HWC>), dim3((a.env1 - a.env0) * BPE), dim3(PK_FS_WG), 0, s, a);
+    return hipGetLastError();
+}
+
+// scale 1, 2, 4; depth 1..8 in CHW and 1, 2, 4, 8 in HWC (pk_fstack_create checks): at depth 1 the
+// two layouts are the same bytes
+hipError_t pk_launch_fstack(const PkStackArgs& a, hipStream_t s) {
+    const u32 d = a.layout && a.depth > 1u ? a.depth : 0u;
+    switch (a.scale * 16u + d) {
+    case 16u: return pk_fs_launch<1u, 16u, false>(a, s);
+    case 32u: return pk_fs_launch<2u, 16u, false>(a, s);
+    case 64u: return pk_fs_launch<4u, 8u, false>(a, s);
+    case 16u + 2u: return pk_fs_launch<1u, 8u, true>(a, s);
+    case 16u + 4u: return pk_fs_launch<1u, 4u, true>(a, s);
+    case 16u + 8u: return pk_fs_launch<1u, 2u, true>(a, s);
+    case 32u + 2u: return pk_fs_launch<2u, 8u, true>(a, s);
+    case 32u + 4u: return pk_fs_launch<2u, 4u, true>(a, s);
+    case 32u + 8u: return pk_fs_launch<2u, 2u, true>(a, s);
+    case 64u + 2u: return pk_fs_launch<4u, 8u, true>(a, s);
+    case 64u + 4u: return pk_fs_launch<4u, 4u, true>(a, s);
+    case 64u + 8u: return pk_fs_launch<4u, 2u, true>(a, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Archive exchange (pk_archive_pack / pk_archive_merge): cells as records and whole-slot payloads.
 
 // pk_archive_pack, one workgroup: the records of cells [cell0, cell0 + count) and, by a scan in cell

@@ -357,3 +357,18 @@ struct PkCountArgs {
     uint32_t env0, env1;
     uint32_t peek, foreign, delta;
 };
+
+// Frame stack (pk_fstack_*): per env D planes of H x W = (144 / s) x (160 / s) bytes, plane 0 the
+// newest, as u8[n][D][H][W] (CHW) or u8[n][H][W][D] (HWC).  A thread of the push owns one piece of
+// consecutive output pixels of one row: 16 pixels at s = 1 and 2 and 8 at s = 4 in CHW (a 16- or
+// 8-byte piece in each plane), 16 / D pixels in HWC (one 16-byte piece that holds their D bytes).
+#define PK_FS_MAX_DEPTH 8u
+
+struct PkStackArgs {
+    const uint8_t* screen;       // [..][144][160], 16-byte aligned: the handle's or the caller's
+    const uint8_t* mask;         // caller's [n] or null
+    uint8_t* stack;              // [n][D * H * W]
+    uint32_t env0, env1;
+    uint32_t scale, depth, layout, mode;
+    uint32_t fill_only;
+};

@@ -16,6 +16,7 @@ import torch
 
 from . import _native
 from .info import NFIELDS, event_dicts, info_dict
+from .spaces import stack_shape
 from ._native import (COLS, ERR_EXCEPTIONS, OBS_SHAPE, PK_F_RELOAD_ON_RESET, PK_F_RENDER, PK_F_REWARD, ROWS,
                       STATE_V9_BYTES, check)
 
@@ -26,6 +27,13 @@ class _CudaArray:
     def __init__(self, ptr: int, shape, typestr: str):
         self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr,
                                          "data": (ptr, False), "version": 2, "strides": None}
+
+
+class _HostArray:
+    """__array_interface__ shim: the same for a handle whose buffers are host memory (device cpu)."""
+
+    def __init__(self, ptr: int, shape, typestr: str):
+        self.__array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (ptr, False), "version": 3}
 
 
 def _u8p(buf: bytes | bytearray | np.ndarray):
@@ -475,6 +483,52 @@ class BatchedEmulator:
         """Empty the table (pk_counts_clear, on the current stream)."""
         check(self._L.pk_counts_clear(self._h, self._stream()), "pk_counts_clear")
 
+    # -- frame stack (stream-ordered except create) ----------------------------------------
+    def _view(self, ptr: int, shape, typestr: str) -> torch.Tensor:
+        """A tensor over a handle-owned buffer on the handle's device, without a copy."""
+        if self.device.type == "cpu":
+            return torch.from_numpy(np.asarray(_HostArray(ptr, shape, typestr)))
+        return torch.as_tensor(_CudaArray(ptr, shape, typestr), device=self.device)
+
+    def stack_create(self, scale: int = 2, depth: int = 4, layout: str = "chw", mode: str = "mean"):
+        """Give the handle a frame stack: per env `depth` frames downscaled by `scale` (1, 2, 4), newest
+        first, uint8 (n, depth, 144 / scale, 160 / scale) for layout "chw" or (n, 144 / scale,
+        160 / scale, depth) for "hwc" (depth 1, 2, 4, 8); mode "mean" averages a scale x scale block,
+        "pick" takes its top left pixel (pk_fstack_create; once, synchronous; any handle).  `stack`
+        is the tensor, all zeros until the first stack_push."""
+        shape = stack_shape(scale, depth, layout)
+        if mode not in ("mean", "pick"):
+            raise ValueError("stack mode must be 'mean' or 'pick'")
+        check(self._L.pk_fstack_create(self._h, int(scale), int(depth),
+                                       _native.PK_FSTACK_HWC if layout == "hwc" else _native.PK_FSTACK_CHW,
+                                       _native.PK_FSTACK_PICK if mode == "pick" else _native.PK_FSTACK_MEAN), "pk_fstack_create")
+        self._stack = self._view(self._L.pk_fstack_ptr(self._h), (self.n,) + shape, "|u1")
+
+    @property
+    def stack(self) -> torch.Tensor | None:
+        """The frame stack, a view of the handle's buffer (pk_fstack_ptr); None without stack_create."""
+        return getattr(self, "_stack", None)
+
+    def stack_push(self, mask: torch.Tensor | None = None, fill_only: bool = False, screen: torch.Tensor | None = None,
+                   env0: int = 0, count: int | None = None):
+        """Push the current frame of the envs of the range onto their stacks, in place and in one
+        launch (pk_fstack_push, on the current stream).  mask: a full-size uint8 (n,) tensor; an env
+        with mask[e] != 0 is filled — all its planes become the new frame — the others are pushed.
+        fill_only=True touches only the envs with mask[e] != 0 (no mask: the whole range) and fills
+        them.  screen: a uint8 (n, 144, 160) tensor to read in the place of the emulator's own
+        screen (which needs render=True).  Returns `stack`."""
+        count = self.n - env0 if count is None else count
+        sp = None
+        if screen is not None:
+            if (screen.dtype != torch.uint8 or screen.device != self.device or tuple(screen.shape) != (self.n, ROWS, COLS)
+                    or not screen.is_contiguous()):
+                raise ValueError("screen must be a contiguous uint8 (n_envs, 144, 160) tensor on the emulator's device")
+            sp = ctypes.c_void_p(screen.data_ptr())
+        check(self._L.pk_fstack_push(self._h, sp, self._full(mask, torch.uint8, "mask"),
+                                     _native.PK_FSTACK_FILL_ONLY if fill_only else 0, env0, count, self._stream()),
+              "pk_fstack_push")
+        return self.stack
+
     # -- action trajectories (stream-ordered except enable) -------------------------------
     def traj_enable(self):
         """Record every env's actions from here on (pk_traj_enable; once, synchronous).  Call it
@@ -677,6 +731,7 @@ class BatchedEmulator:
             self.obs = None
             self.errors = None
             self.info = self.info_flag = self.heatmap = self.info_bits = None
+            self._stack = None
             self._L.pk_destroy(self._h)
             self._h = None
 

@@ -265,7 +265,8 @@ class VecEnv:
                  fork_slots: int = 0, archive_cells: int = 0, archive_seed: int = 0, archive_shift: int = 0,
                  record_trajectories: bool = False, archive_exchange: bool = False, archive_key: str = "ram",
                  archive_frame=(16, 16, 8), novelty_log2: int = 0, novelty_beta: float = 1.0, novelty_key: str = "frame",
-                 novelty_frame=(16, 16, 8)):
+                 novelty_frame=(16, 16, 8), frame_stack: int = 0, stack_scale: int = 2, stack_layout: str = "chw",
+                 stack_mode: str = "mean"):
         """reward=False: the screen-obs env of configs[3] — obs is the (144, 160) u8 screen, rewards are
         0 and episodes end at max_episode_steps.  power_on=True starts (and resets) every env from
         the cartridge's power-on state instead of a savestate.
@@ -317,7 +318,20 @@ class VecEnv:
         sub-batch takes its keys on its own stream right after its step; the table, one shared
         structure, is updated where calls are in one order: inside step() in batch order, and in the
         recv() that returns a sub-batch.  novelty_keys / novelty_counts / novelty_bonus are the last
-        values per env; counts_sync() adds up the tables of a torch.distributed group."""
+        values per env; counts_sync() adds up the tables of a torch.distributed group.
+
+        frame_stack=D (1..8; 0 = off; needs a rendering emulator) makes the observation a frame stack kept
+        on the device (pk_fstack_*): the last D frames of every env, newest first, downscaled by
+        stack_scale (1, 2, 4; stack_mode "mean" averages a block, "pick" takes its top left pixel, the
+        reference's [::2, ::2]) — uint8 (D, 144 / s, 160 / s) for stack_layout "chw", (144 / s, 160 / s, D)
+        for "hwc" (D = 1, 2, 4, 8; D = 4 at scale 2 is the reference observation's shape) — with or
+        without the reward stack, on any cartridge.  reset(), step(), recv() and async_reset() return it
+        in the place of the composite observation or the screen.  Each sub-batch pushes the frame its
+        step ended on, on its own stream and in one launch; an env that finished returns D copies of
+        the first frame of its next episode.  reset() fills every env, and load_from_bank,
+        resume_from_bank, fork, archive_explore and load_state refill the envs whose machine they
+        replaced (load_from_bank: every env it names with a slot of the bank).  With 0 nothing is
+        allocated or launched."""
         self.batch_size = batch_size or num_envs
         if num_envs % self.batch_size:
             raise ValueError("batch_size must divide num_envs")
@@ -347,6 +361,15 @@ class VecEnv:
                                  for b in range(self.num_batches)]).to(self.device) if self._padded else None)
         self.single_observation_space = (spaces.observation_space() if getattr(emulator, "reward", True)
                                          else spaces.screen_space())
+        self.frame_stack = 0 if frame_stack is None else frame_stack
+        self.stack_scale, self.stack_layout, self.stack_mode = stack_scale, stack_layout, stack_mode
+        if self.frame_stack != 0:
+            self.single_observation_space = spaces.stack_space(stack_scale, frame_stack, stack_layout)
+            if stack_mode not in ("mean", "pick"):
+                raise ValueError("stack_mode must be 'mean' or 'pick'")
+            if not getattr(emulator, "render", True):
+                raise ValueError("frame_stack needs an emulator that renders (render=True)")
+            self.emu.stack_create(stack_scale, frame_stack, stack_layout, stack_mode)
         self.single_action_space = spaces.action_space()
         self.env_ids = torch.arange(env_offset, env_offset + num_envs, device=self.device)
         self.masks = torch.ones(num_envs, dtype=torch.bool, device=self.device)
@@ -501,7 +524,10 @@ class VecEnv:
         like save_to_bank's.  An empty or out-of-range slot leaves its env alone and counts in
         emu.bank_rejects()."""
         self._join_streams()
-        self.emu.bank_load(self._bank_map(envs, slots))
+        m = self._bank_map(envs, slots)
+        self.emu.bank_load(m)
+        if self.frame_stack:
+            self.emu.stack_push(((m >= 0) & (m < self.emu.bank_slots)).to(torch.uint8), fill_only=True)
 
     def _episode_args(self, envs, slots):
         if self._ck_return is None:
@@ -546,9 +572,13 @@ class VecEnv:
         ok = self._ck_valid[slots]           # the envs the device does not reject
         self.stats.ep_return[envs] = torch.where(ok, self._ck_return[slots], self.stats.ep_return[envs])
         self.stats.ep_length[envs] = torch.where(ok, self._ck_length[slots], self.stats.ep_length[envs])
+        phys = (envs // self.batch_size) * self.slot + envs % self.batch_size
         if self._slots is not None:
-            phys = (envs // self.batch_size) * self.slot + envs % self.batch_size
             self._slots[phys] = torch.where(ok, self._ck_slots[slots], self._slots[phys])
+        if self.frame_stack:                 # the resumed envs start a history of their own
+            m = torch.zeros(self.emu.n, dtype=torch.uint8, device=self.device)
+            m[phys] = ok.to(torch.uint8)
+            self.emu.stack_push(m, fill_only=True)
 
     def fork(self, dst_envs, src_envs, check: bool = True):
         """Copy the running episode of env src_envs[i] over env dst_envs[i]: every distinct source
@@ -645,6 +675,8 @@ class VecEnv:
         self._join_streams()
         mask = self._physical(torch.as_tensor(mask, device=self.device) != 0, 0, torch.uint8)
         self.emu.archive_explore(mask, out=self._arch_out)
+        if self.frame_stack:                 # the envs that resumed: the device's own answer, rejects excluded
+            self.emu.stack_push((self._arch_out >= 0).to(torch.uint8), fill_only=True)
         drawn = self._logical(self._arch_out).long()
         last = self._ck_return.numel() - 1
         slots = torch.where(drawn >= 0, drawn, last)
@@ -789,6 +821,12 @@ class VecEnv:
         """Emulator index of env."""
         return (env // self.batch_size) * self.slot + env % self.batch_size
 
+    def _obs_buffer(self) -> torch.Tensor:
+        """What the envs observe, in emulator order: the frame stack, the composite observation or the screen."""
+        if self.frame_stack:
+            return self.emu.stack
+        return self.emu.obs if self.emu.reward else self.emu.screen
+
     def _logical(self, obs: torch.Tensor) -> torch.Tensor:
         return obs.index_select(0, self._phys) if self._padded else obs
 
@@ -819,6 +857,8 @@ class VecEnv:
             for b in range(self.num_batches):
                 self._draw_slots(self._prange(b))
             obs = self._logical(self.emu.reset_from(self._slots))
+        if self.frame_stack:
+            obs = self._logical(self.emu.stack_push(fill_only=True))
         self.t = 0
         self._log_wait = 0
         if self.sticky_errors is not None:
@@ -946,6 +986,8 @@ class VecEnv:
             self.emu.reset(term)
         else:
             self.emu.reset_range(psl.start, self.batch_size, self.emu.terminals)
+        if self.frame_stack:        # one launch: the finished envs fill from their reset frame, the others push
+            obs = self.emu.stack_push(self.emu.terminals, env0=psl.start, count=self.batch_size)[psl]
         return obs, rewards, terminals, truncations
 
     def _log(self, deferred: bool = False):
@@ -1010,7 +1052,7 @@ class VecEnv:
             obs, rewards, terminals, truncations = self._step_range(0, a, True)
         else:
             outs = [self._step_range(b, a[self._range(b)], True) for b in range(self.num_batches)]
-            obs = self._logical(self.emu.obs if self.emu.reward else self.emu.screen)
+            obs = self._logical(self._obs_buffer())
             rewards = torch.cat([o[1] for o in outs])
             terminals = torch.cat([o[2] for o in outs])
             truncations = torch.cat([o[3] for o in outs])
@@ -1025,6 +1067,11 @@ class VecEnv:
     def load_state(self, env: int, state: bytes):
         """Install a v9 savestate into one env (pk_load_env; pyboy_binding.py:59-69)."""
         self.emu.load_env(self.phys(env), state)
+        if self.frame_stack:
+            self._join_streams()
+            m = torch.zeros(self.emu.n, dtype=torch.uint8, device=self.device)
+            m[self.phys(env)] = 1
+            self.emu.stack_push(m, fill_only=True)
 
     def video_recorder(self, envs, capacity: int = 1024):
         """A FrameRecorder (pokegym_amd/video.py) of the given envs' screens: call .capture() after
@@ -1089,7 +1136,7 @@ class VecEnv:
             psl = self._prange(b)   # (a counts_sync() in between has counted the sub-batch already)
             rew = rew + (self._novelty_count(psl) if self._nov_due[b] == 1 else self._nov_bonus[psl])
             self._nov_due[b] = 0
-        obs = self.emu.obs if self.emu.reward else self.emu.screen
+        obs = self._obs_buffer()
         infos, self._pending_infos = getattr(self, "_pending_infos", []) + logged, []
         return obs[self._prange(b)], rew, term, trunc, infos, self.env_ids[sl], self.masks[sl]
 

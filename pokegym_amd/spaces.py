@@ -45,3 +45,23 @@ def screen_space():
     """The full-resolution grey screen (screen.screen_ndarray()[:, :, 0], environment.py:268) that
     the screen-obs configuration returns instead of the (72, 80, 4) composite."""
     return Box(low=0, high=255, shape=(144, 160), dtype=np.uint8)
+
+
+def stack_shape(scale: int = 2, depth: int = 4, layout: str = "chw"):
+    """Shape of one env's frame stack (pk_fstack_create); ValueError for a geometry it does not take."""
+    if scale not in (1, 2, 4):
+        raise ValueError("stack scale must be 1, 2 or 4")
+    if layout not in ("chw", "hwc"):
+        raise ValueError("stack layout must be 'chw' or 'hwc'")
+    if isinstance(depth, bool) or not isinstance(depth, (int, np.integer)) or not 1 <= depth <= 8:
+        raise ValueError("stack depth must be 1..8")
+    if layout == "hwc" and depth not in (1, 2, 4, 8):
+        raise ValueError("stack depth must be 1, 2, 4 or 8 with layout 'hwc'")
+    h, w = 144 // scale, 160 // scale
+    return (int(depth), h, w) if layout == "chw" else (h, w, int(depth))
+
+
+def stack_space(scale: int = 2, depth: int = 4, layout: str = "chw"):
+    """The frame stack VecEnv(frame_stack=depth) returns: depth downscaled frames, newest first —
+    (depth, 144 / scale, 160 / scale) for "chw", (144 / scale, 160 / scale, depth) for "hwc"."""
+    return Box(low=0, high=255, shape=stack_shape(scale, depth, layout), dtype=np.uint8)
