@@ -23,6 +23,7 @@
 hipError_t pk_launch_step(const PkStepArgs& a, hipStream_t s);
 hipError_t pk_launch_step_small(const PkStepArgs& a, hipStream_t s);   // pk_step.hip built with PK_K1_SMALL
 hipError_t pk_launch_render(const PkStepArgs& a, hipStream_t s);
+hipError_t pk_launch_render_done(const PkStepArgs& a, const PkDoneArgs& d, hipStream_t s);
 hipError_t pk_launch_reset(const PkResetArgs& a, hipStream_t s);
 hipError_t pk_launch_list(const uint8_t* mask, uint32_t env0, uint32_t env1, uint32_t* cnt, uint32_t* ids, hipStream_t s);
 hipError_t pk_launch_render_latched(const PkStepArgs& a, hipStream_t s);
@@ -876,14 +877,24 @@ int pk_step_range(pk_handle* h, uint32_t env0, uint32_t count, const uint8_t* ac
         HIPCHK(pk_launch_traj_record(t, s));
     }
     if (h->prof && (rc = prof_event(h, s))) return rc;
-    if (a.render_last) HIPCHK(pk_launch_render(a, s));
+    // a rendered step without the reward stack: K2 writes the termination flags too
+    const bool fuse_done = a.render_last && !(h->flags & PK_F_REWARD) && (rew || term || trunc);
+    if (fuse_done) {
+        PkDoneArgs d;
+        d.time_reg = h->regs + (size_t)PK_R_TIME * h->npad;
+        d.term = term; d.trunc = trunc; d.rew = rew;
+        d.max_steps = h->max_steps; d.on = 1u;
+        HIPCHK(pk_launch_render_done(a, d, s));
+    } else if (a.render_last) {
+        HIPCHK(pk_launch_render(a, s));
+    }
     if (h->prof && (rc = prof_event(h, s))) return rc;
     if (h->flags & PK_F_REWARD) {
         PkRewardArgs r = reward_args(h, env0, env1);
         r.actions = actions; r.rew = rew; r.term = term; r.trunc = trunc;
         HIPCHK(pk_launch_reward(r, s));
         HIPCHK(pk_launch_obs(r, s));
-    } else if (rew || term || trunc) {
+    } else if (!fuse_done && (rew || term || trunc)) {
         HIPCHK(pk_launch_done(h->regs + (size_t)PK_R_TIME * h->npad + env0, count, h->max_steps, term ? term + env0 : nullptr,
                               trunc ? trunc + env0 : nullptr, rew ? rew + env0 : nullptr, s));
     }

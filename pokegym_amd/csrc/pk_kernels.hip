@@ -22,12 +22,22 @@
 // ---------------------------------------------------------------------------------------------
 // K2: rasterise the latched lines of the rendered frame.  One wave = one (group, scanline),
 // lane = env: the 64 lanes read the same VRAM offsets of their interleaved images (coalesced).
-__global__ void __launch_bounds__(64) pk_render_kernel(PkStepArgs A) {
+// The line is rasterised in registers (pk_render.h render_line_regs; K1's flush_lines keeps the
+// byte-array render_line).  With D.on the wave of scanline 0 also writes its envs' termination
+// flags, what pk_done_kernel writes, so a rendered step without the reward stack needs no launch
+// for them.
+__global__ void __launch_bounds__(64) pk_render_kernel(PkStepArgs A, PkDoneArgs D) {
     const u32 y = blockIdx.x % PK_ROWS;
     const u32 gid = A.env0 / PK_LANES + blockIdx.x / PK_ROWS;
     const u32 lane = threadIdx.x;
     const u32 env = gid * PK_LANES + lane;
     if (env >= A.env1) return;
+    if (D.on && y == 0u) {
+        const u8 done = D.time_reg[env] >= D.max_steps ? 1 : 0;
+        if (D.term) D.term[env] = done;
+        if (D.trunc) D.trunc[env] = done;
+        if (D.rew) D.rew[env] = 0.0;
+    }
     const u32 rf = A.regs[PK_R_RFLAGS * A.npad + env];
     u8* out = A.screen + (size_t)env * PK_SCREEN + y * PK_COLS;
     const u32 idx = (gid * PK_ROWS + y) * PK_LANES + lane;
@@ -40,8 +50,8 @@ __global__ void __launch_bounds__(64) pk_render_kernel(PkStepArgs A) {
         return;
     }
     if (!(l2 & 0x100u)) return;
-    const Mem m = mem_view(A.mem, env, A.ilv_sh);
-    render_line(m, y, A.lat[idx], A.lat[A.lat_stride + idx], (int)(l2 & 0xFFu) - 1, out);
+    const MemW m = memw_view(A.mem, gid, lane, A.ilv_sh);
+    render_line_regs(m, y, A.lat[idx], A.lat[A.lat_stride + idx], (int)(l2 & 0xFFu) - 1, out);
     A.lat[2u * A.lat_stride + idx] = l2 & ~0x100u;
 }
 
@@ -128,10 +138,17 @@ __global__ void pk_scatter_env_kernel(u8* mem, u32 env, u32 sh, const u8* in) {
 
 // ---------------------------------------------------------------------------------------------
 // host-side launchers (called by the C ABI in pk_capi.cpp)
-hipError_t pk_launch_render(const PkStepArgs& a, hipStream_t s) {
+// d.on: also write the range's termination flags (pk_launch_done's work)
+hipError_t pk_launch_render_done(const PkStepArgs& a, const PkDoneArgs& d, hipStream_t s) {
     const u32 grid = ((a.env1 - a.env0 + PK_LANES - 1u) / PK_LANES) * PK_ROWS;
-    hipLaunchKernelGGL(pk_render_kernel, dim3(grid), dim3(PK_LANES), 0, s, a);
+    hipLaunchKernelGGL(pk_render_kernel, dim3(grid), dim3(PK_LANES), 0, s, a, d);
     return hipGetLastError();
+}
+
+hipError_t pk_launch_render(const PkStepArgs& a, hipStream_t s) {
+    PkDoneArgs d;
+    memset(&d, 0, sizeof d);
+    return pk_launch_render_done(a, d, s);
 }
 
 hipError_t pk_launch_render_latched(const PkStepArgs& a, hipStream_t s) {

@@ -154,6 +154,17 @@ struct PkStepArgs {
     uint32_t all_staged;      // every ROM bank is staged in this kernel's LDS slots (the ALL instance)
 };
 
+// K2's second argument block: the termination flags of a rendered step without the reward stack
+// (pk_done_kernel's outputs), written by the wave of scanline 0 when `on` is set
+struct PkDoneArgs {
+    const uint32_t* time_reg;    // regs + PK_R_TIME * npad
+    uint8_t* term;               // caller's [n] arrays, each may be null
+    uint8_t* trunc;
+    double* rew;
+    uint32_t max_steps;
+    uint32_t on;
+};
+
 struct PkResetArgs {
     uint8_t* mem;
     uint32_t* regs;

@@ -140,6 +140,227 @@ __device__ inline void render_line(const Mem& m, u32 y, u32 lat0, u32 lat1, int 
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// K2's rasteriser: the same line as render_line, held in registers.  A line is two bit planes of
+// 160 bits (five words each): pixel p is bit p & 31 of word p >> 5, plane 0 the low and plane 1 the
+// high bit of its 2-bit value.  Tiles are decoded eight pixels at a time with whole-word operations,
+// every array below is indexed by compile-time constants only (the loops are fully unrolled), so
+// the line never leaves the VGPRs.
+#ifdef __HIPCC__
+__device__ __forceinline__ u32 pk_alignbit(u32 hi, u32 lo, u32 sh) { return __builtin_amdgcn_alignbit(hi, lo, sh); }
+__device__ __forceinline__ u32 pk_brev32(u32 v) { return __builtin_bitreverse32(v); }
+#else
+// ({hi, lo} >> (sh & 31))[31:0]
+static inline u32 pk_alignbit(u32 hi, u32 lo, u32 sh) { return (u32)((((uint64_t)hi << 32) | lo) >> (sh & 31u)); }
+static inline u32 pk_brev32(u32 v) {
+    v = ((v >> 1) & 0x55555555u) | ((v & 0x55555555u) << 1);
+    v = ((v >> 2) & 0x33333333u) | ((v & 0x33333333u) << 2);
+    v = ((v >> 4) & 0x0F0F0F0Fu) | ((v & 0x0F0F0F0Fu) << 4);
+    return (v >> 24) | ((v >> 8) & 0xFF00u) | ((v << 8) & 0xFF0000u) | (v << 24);
+}
+#endif
+// bits of a where the mask is set, of b elsewhere (v_bfi_b32)
+__device__ __forceinline__ u32 bsel(u32 mask, u32 a, u32 b) { return (a & mask) | (b & ~mask); }
+// all ones when bit k of v is set
+__device__ __forceinline__ u32 bit_fill(u32 v, u32 k) { return 0u - ((v >> k) & 1u); }
+
+// A lane's view of its image through a base that is the same for the whole wave (the group's) and a
+// 32-bit offset, so the loads take the scalar-base form: byte(phys) = gb[lo + (phys << sh)]
+struct MemW {
+    const u8* gb;   // the group's base (wave-uniform in K2)
+    u32 lo;         // the lane's offset inside the group
+    u32 sh;         // interleave shift
+};
+__device__ __forceinline__ u32 ldw(const MemW& m, u32 phys) { return m.gb[m.lo + (phys << m.sh)]; }
+// the view of lane l of group gid
+__device__ __forceinline__ MemW memw_view(const u8* mem, u32 gid, u32 l, u32 sh) {
+    MemW m;
+    m.gb = mem + (uint64_t)gid * pk_group_stride(sh);
+    m.lo = (l >> sh) * (u32)pk_sub_stride(sh) + (l & ((1u << sh) - 1u));
+    m.sh = sh;
+    return m;
+}
+
+// Row `fine` of 21 neighbouring tiles of one map row (phys address maprow), from tile column c0 on
+// and wrapping at 32: the colour-index planes of their 168 pixels.  The 21st tile is read only
+// when the caller's fine scroll needs it.  Every address stays inside VRAM whatever the inputs.
+__device__ __forceinline__ void tile_planes(const MemW& m, u32 maprow, u32 c0, u32 lcdc, u32 fine, bool last,
+                                            u32 (&pl)[6], u32 (&ph)[6]) {
+    // signed ids (LCDC.4 = 0): 0x1000 + (int8)t * 16 = ((t ^ 0x80) << 4) + 0x800
+    const u32 flip = (lcdc & 0x10u) ? 0u : 0x80u;
+    const u32 base = PK_P_VRAM + ((lcdc & 0x10u) ? 0u : 0x800u) + fine * 2u;
+    u32 t[21], lo[24], hi[24];
+#pragma unroll
+    for (u32 k = 0; k < 21u; k++) t[k] = (k < 20u || last) ? ldw(m, maprow + ((c0 + k) & 31u)) : 0u;
+#pragma unroll
+    for (u32 k = 0; k < 24u; k++) {
+        lo[k] = hi[k] = 0u;
+        if (k < 20u || (k == 20u && last)) {
+            const u32 ta = base + ((t[k] ^ flip) << 4);
+            lo[k] = ldw(m, ta);
+            hi[k] = ldw(m, ta + 1u);
+        }
+    }
+    // four tiles a word: a tile's leftmost pixel is bit 7 of its bytes, so reverse the bits of the
+    // word and put the bytes back in order
+#pragma unroll
+    for (u32 i = 0; i < 6u; i++) {
+        const u32 a = lo[4 * i] | (lo[4 * i + 1] << 8) | (lo[4 * i + 2] << 16) | (lo[4 * i + 3] << 24);
+        const u32 b = hi[4 * i] | (hi[4 * i + 1] << 8) | (hi[4 * i + 2] << 16) | (hi[4 * i + 3] << 24);
+        pl[i] = __builtin_amdgcn_perm(0u, pk_brev32(a), 0x00010203u);
+        ph[i] = __builtin_amdgcn_perm(0u, pk_brev32(b), 0x00010203u);
+    }
+}
+
+// the most objects a line shows
+#define PK_OBJ_LINE 10
+
+// one scanline of one lane, arguments as render_line's; out is 16-byte aligned
+__device__ __forceinline__ void render_line_regs(const MemW& m, u32 y, u32 lat0, u32 lat1, int lw, u8* out) {
+    const u32 lcdc = lat0 & 0xFFu;
+    const u32 bx = bfe8(lat0, 8), by = bfe8(lat0, 16);
+    const int wx = (int)bfe8(lat0, 24) - 7, wy = (int)(lat1 & 0xFFu);
+    const u32 bgp = bfe8(lat1, 8), obp0 = bfe8(lat1, 16), obp1 = bfe8(lat1, 24);
+    // (a window that starts right of the screen shows nothing)
+    const bool win = (lcdc & 0x20u) && wy <= (int)y && wx < (int)PK_COLS;
+    const bool bgon = (lcdc & 0x01u) != 0u;
+    u32 c0[5], c1[5];   // colour indices of the BG / window pixels
+#pragma unroll
+    for (u32 i = 0; i < 5u; i++) c0[i] = c1[i] = 0u;
+    // background: the fine scroll is a funnel shift of the tile stream
+    if (bgon && !(win && wx <= 0)) {
+        const u32 yy = y + by, fs = bx & 7u;
+        u32 pl[6], ph[6];
+        tile_planes(m, PK_P_VRAM + ((lcdc & 0x08u) ? 0x1C00u : 0x1800u) + ((yy >> 3) & 31u) * 32u, bx >> 3, lcdc, yy & 7u,
+                    fs != 0u, pl, ph);
+#pragma unroll
+        for (u32 i = 0; i < 5u; i++) {
+            c0[i] = pk_alignbit(pl[i + 1], pl[i], fs);
+            c1[i] = pk_alignbit(ph[i + 1], ph[i], fs);
+        }
+    }
+    // window: the same stream, its pixel 0 at screen column wx (from -7 on), merged by a mask of
+    // the columns from wx on
+    u32 wm[5];
+#pragma unroll
+    for (u32 i = 0; i < 5u; i++) wm[i] = 0u;
+    if (win) {
+        const u32 lwu = (u32)lw & 0xFFu, nwx = (u32)(-wx), fs = nwx & 7u;   // column x shows window pixel x + nwx
+        u32 pl[6], ph[6];
+        tile_planes(m, PK_P_VRAM + ((lcdc & 0x40u) ? 0x1C00u : 0x1800u) + ((lwu >> 3) & 31u) * 32u, (u32)((int)nwx >> 3), lcdc,
+                    lwu & 7u, fs != 0u, pl, ph);
+#pragma unroll
+        for (u32 i = 0; i < 5u; i++) {
+            int n = wx - (int)(32u * i);   // columns of this word left of the window
+            n = n < 0 ? 0 : (n > 32 ? 32 : n);
+            wm[i] = (0xFFFFFFFFu << ((u32)n >> 1)) << ((u32)n - ((u32)n >> 1));
+            c0[i] = bsel(wm[i], pk_alignbit(pl[i + 1], pl[i], fs), c0[i]);
+            c1[i] = bsel(wm[i], pk_alignbit(ph[i + 1], ph[i], fs), c1[i]);
+        }
+    }
+    // BGP on the planes: shade bit b of colour c is bit 2c + b of the palette.  With the BG
+    // disabled only the window's pixels keep their shade, the rest is shade 0.
+    u32 s0[5], s1[5];
+    {
+        const u32 p00 = bit_fill(bgp, 0), p01 = bit_fill(bgp, 1), p10 = bit_fill(bgp, 2), p11 = bit_fill(bgp, 3);
+        const u32 p20 = bit_fill(bgp, 4), p21 = bit_fill(bgp, 5), p30 = bit_fill(bgp, 6), p31 = bit_fill(bgp, 7);
+        const u32 keep = bgon ? 0xFFFFFFFFu : 0u;
+#pragma unroll
+        for (u32 i = 0; i < 5u; i++) {
+            s0[i] = bsel(c1[i], bsel(c0[i], p30, p20), bsel(c0[i], p10, p00)) & (wm[i] | keep);
+            s1[i] = bsel(c1[i], bsel(c0[i], p31, p21), bsel(c0[i], p11, p01)) & (wm[i] | keep);
+        }
+    }
+    if (lcdc & 0x02u) {
+        // one pass over the OAM: the first ten objects on this line in OAM order, kept sorted by
+        // (X, OAM index) descending in registers: key = X << 16 | index << 8 | Y (never 0: Y = 0
+        // is on no line), 0 = empty
+        const u32 h = (lcdc & 0x04u) ? 16u : 8u;
+        u32 K[PK_OBJ_LINE];
+#pragma unroll
+        for (u32 i = 0; i < PK_OBJ_LINE; i++) K[i] = 0u;
+        u32 ns = 0;
+#pragma unroll
+        for (u32 n0 = 0; n0 < 40u; n0 += 10u) {
+            u32 oy[10], ox[10];
+#pragma unroll
+            for (u32 k = 0; k < 10u; k++) {
+                oy[k] = ldw(m, PK_P_OAM + (n0 + k) * 4u);
+                ox[k] = ldw(m, PK_P_OAM + (n0 + k) * 4u + 1u);
+            }
+#pragma unroll
+            for (u32 k = 0; k < 10u; k++) {
+                if (y + 16u - oy[k] < h && ns < PK_OBJ_LINE) {
+                    ns++;
+                    u32 key = (ox[k] << 16) | ((n0 + k) << 8) | oy[k];
+#pragma unroll
+                    for (u32 i = 0; i < PK_OBJ_LINE; i++) {
+                        const u32 a = K[i];
+                        K[i] = a > key ? a : key;
+                        key = a > key ? key : a;
+                    }
+                }
+            }
+        }
+        // draw from the lowest priority (largest X, then largest index) to the highest
+        const u32 b0 = bit_fill(bgp, 0), b1 = bit_fill(bgp, 1);   // the shade of BG colour 0
+        while (K[0] != 0u) {
+            const u32 key = K[0];
+#pragma unroll
+            for (u32 i = 0; i + 1u < PK_OBJ_LINE; i++) K[i] = K[i + 1];
+            K[PK_OBJ_LINE - 1] = 0u;
+            const u32 base = PK_P_OAM + ((key >> 8) & 0xFFu) * 4u;
+            u32 ti = ldw(m, base + 2u);
+            const u32 at = ldw(m, base + 3u);
+            if (h == 16u) ti &= 0xFEu;
+            const u32 dy = y + 16u - (key & 0xFFu);
+            const u32 yy = (at & 0x40u) ? (h - 1u - dy) : dy;
+            const u32 ta = PK_P_VRAM + ti * 16u + yy * 2u;
+            const u32 w = ldw(m, ta) | (ldw(m, ta + 1u) << 8);
+            // pixel k of the object is bit k: the bytes bit-reversed, or as they are under an X flip
+            const u32 r = pk_brev32(w);
+            const u32 ol = (at & 0x20u) ? (w & 0xFFu) : (r >> 24), oh = (at & 0x20u) ? (w >> 8) : ((r >> 16) & 0xFFu);
+            const u32 pal = (at & 0x10u) ? obp1 : obp0;
+            // colour 0 is transparent; the palette on the planes as above
+            const u32 om = ol | oh;
+            const u32 v0 = bsel(oh, bsel(ol, bit_fill(pal, 6), bit_fill(pal, 4)), ol & bit_fill(pal, 2)) & om;
+            const u32 v1 = bsel(oh, bsel(ol, bit_fill(pal, 7), bit_fill(pal, 5)), ol & bit_fill(pal, 3)) & om;
+            // the object's eight pixels start at column X - 8: a 32-column word left of the screen
+            // takes what is clipped there, the words past the last one what is clipped on the right
+            const u32 pos = (key >> 16) + 24u, j0 = pos >> 5, sft = pos & 31u;
+            const u32 mlo = om << sft, mhi = (om >> 1) >> (31u - sft);
+            const u32 v0lo = v0 << sft, v0hi = (v0 >> 1) >> (31u - sft);
+            const u32 v1lo = v1 << sft, v1hi = (v1 >> 1) >> (31u - sft);
+            const u32 front = (at & 0x80u) ? 0u : 0xFFFFFFFFu;
+#pragma unroll
+            for (u32 i = 0; i < 5u; i++) {
+                const bool isl = j0 == i + 1u, ish = j0 == i;
+                u32 mk = isl ? mlo : (ish ? mhi : 0u);
+                // attribute bit 7: only over pixels that show the shade of BG colour 0 now
+                mk &= front | ~((s0[i] ^ b0) | (s1[i] ^ b1));
+                s0[i] = bsel(mk, isl ? v0lo : v0hi, s0[i]);
+                s1[i] = bsel(mk, isl ? v1lo : v1hi, s1[i]);
+            }
+        }
+    }
+    // grey bytes, four pixels a word: the pixels' plane bits spread to one a byte select the byte of
+    // the palette word FF 99 55 00
+#pragma unroll
+    for (u32 q = 0; q < PK_COLS / 16u; q++) {
+        u32 wv[4];
+#pragma unroll
+        for (u32 j = 0; j < 4u; j++) {
+            const u32 sft = (q & 1u) * 16u + j * 4u;
+            const u32 l4 = (s0[q >> 1] >> sft) & 15u, h4 = (s1[q >> 1] >> sft) & 15u;
+            const u32 sel = ((l4 * 0x00204081u) & 0x01010101u) | (((h4 * 0x00204081u) & 0x01010101u) << 1);
+            wv[j] = __builtin_amdgcn_perm(0u, 0x005599FFu, sel);
+        }
+        uint4 v;
+        v.x = wv[0]; v.y = wv[1]; v.z = wv[2]; v.w = wv[3];
+        *reinterpret_cast<uint4*>(out + q * 16u) = v;
+    }
+}
+
 // host-simulation hooks (design statistics): a flush_lines call (0) and a line it rasterises (1)
 #ifndef PK_FLUSH_STAT
 #define PK_FLUSH_STAT(rendered) ((void)0)
