@@ -640,6 +640,95 @@ uint8_t* pk_fstack_ptr(pk_handle* h);               /* device pointer, owned by 
 int pk_fstack_push(pk_handle* h, const uint8_t* screen_dev, const uint8_t* mask_dev, uint32_t flags,
                    uint32_t env0, uint32_t count, void* stream);
 
+/* RAM probes: a reward, a done flag and a feature vector read from every env's RAM by a small program
+ * given once per handle — the host-side mem_val / bit_count / BCD reads of a reward function, for a
+ * whole range of envs in one launch and on any cartridge.  It needs nothing else: no PK_F_REWARD, no
+ * bank.  Everything is exact in integers; only the reward is a double, with a stated rounding.
+ *
+ * A program is m probes, 1..64.  Probe j has `count` elements, 1..64; element k lies at the guest
+ * addresses [addr + k * stride, addr + k * stride + len) (stride is ignored when count == 1), every
+ * byte of it inside what pk_get_ram accepts — WRAM and its echo, 0xC000-0xFDFF, an element not
+ * wrapping the echo mirror, or HRAM, 0xFF80-0xFFFE.  The value of an element, for any byte values:
+ *   PK_PV_LE    len 1..3    little-endian unsigned
+ *   PK_PV_BE    len 1..3    big-endian unsigned
+ *   PK_PV_BCD   len 1..3    big-endian packed BCD: x = 0, then x = 10 * x + nibble over the 2 * len
+ *                           nibbles, most significant first; a nibble above 9 counts as it is
+ *   PK_PV_BITS  len 1..512  the number of set bits in the len bytes
+ * The probe's value v is the PK_PR_SUM or the PK_PR_MAX of its elements; v < 2^30 by these bounds.
+ *
+ * Per env and probe the handle keeps one u32 word s, 0 after pk_probe_create; its layout is the
+ * kernel's business.  The probe's contribution c to the reward, by op:
+ *   PK_PO_NONE    a feature only: nothing is added, s is never written
+ *   PK_PO_DELTA   c = weight * (double)((int64)v - (int64)s);               then s = v
+ *   PK_PO_NEWMAX  c = v > s ? weight * (double)(v - s) : +0.0;              then s = max(s, v)
+ *   PK_PO_CHANGE  c = v != s ? weight : +0.0;                               then s = v
+ * The done term of a probe compares v with arg as unsigned numbers: PK_PC_NONE (never), EQ, NE, GE,
+ * LE; an env's done is the OR over its probes.  The reward r of an env starts at +0.0 and takes the
+ * contributions of the probes with op != PK_PO_NONE in ascending probe index; every product and every
+ * sum is rounded once to IEEE f64 — no fused multiply-add — so r is the same bits as the same
+ * statements in numpy (pokegym_amd/probes.py model()).
+ *
+ * pk_probe_create (synchronous): once per handle, on any handle; prog_host is a host array of m
+ * pk_probe.  On failure — a second call, m outside 1..64, an unknown kind, reduce, op or cmp, a len
+ * outside its kind's range, a count outside 1..64, a weight that is not finite, an element with a
+ * byte outside the ranges above, out of memory — the handle is unchanged (a later correct call
+ * succeeds).  pk_probe_count is m, 0 without a program.  A handle that never creates one makes
+ * exactly the launches and allocations it made before.
+ *
+ * pk_probe_eval (one launch, stream-ordered, no host sync, no allocation): mask_dev is NULL or a
+ * device u8[n], rew_dev f64[n], term_dev u8[n], feat_dev i32[n][m]; each of the three outputs may be
+ * NULL; all are full size and indexed by env.  The range follows pk_step_range's rule.
+ *   flags == 0: every env of the range takes part.  With mask[e] != 0 the env REBASES: s_j = v_j for
+ *     every probe with op != PK_PO_NONE; its rew and term elements are not touched.  Otherwise (a
+ *     NULL mask included) it EVALUATES: the states move as stated above, rew[e] = rew[e] + r (one
+ *     more rounded sum) and term[e] |= done.
+ *   PK_PROBE_REBASE_ONLY: only the envs with mask[e] != 0 take part (a NULL mask: every env of the
+ *     range), and they rebase; the other envs keep every byte, of state and of outputs.
+ *   PK_PROBE_SET (it only changes what an evaluating env does, so with REBASE_ONLY it does
+ *     nothing): an evaluating env gets rew[e] = r and term[e] = done in the place of the sum and
+ *     the OR.
+ * Row e of feat_dev receives v_0 .. v_{m-1} for every env that takes part, rebasing or evaluating.
+ * Nothing outside the elements of [env0, env0 + count) is written, so disjoint ranges may run
+ * concurrently on different streams.  Bad arguments (no program, unknown flag bits, a range past n,
+ * an env0 that is no multiple of 64) are a negative code with pk_last_error, never a fault, and write
+ * nothing.
+ *
+ * The state belongs to the env, as the frame stack does: bank slots, checkpoints, the archive and
+ * the exchange payload do not carry it and keep their formats.  The caller rebases
+ * (PK_PROBE_REBASE_ONLY) an env whose machine was replaced — a reset, a load, a resume — so a resumed
+ * PK_PO_NEWMAX starts again from the current value; VecEnv(probes=...) does. */
+#define PK_PV_LE 0u
+#define PK_PV_BE 1u
+#define PK_PV_BCD 2u
+#define PK_PV_BITS 3u
+#define PK_PR_SUM 0u
+#define PK_PR_MAX 1u
+#define PK_PO_NONE 0u
+#define PK_PO_DELTA 1u
+#define PK_PO_NEWMAX 2u
+#define PK_PO_CHANGE 3u
+#define PK_PC_NONE 0u
+#define PK_PC_EQ 1u
+#define PK_PC_NE 2u
+#define PK_PC_GE 3u
+#define PK_PC_LE 4u
+#define PK_PROBE_REBASE_ONLY 1u   /* pk_probe_eval flags */
+#define PK_PROBE_SET 2u
+#define PK_PROBE_MAX 64u          /* probes of a program, and elements of a probe */
+typedef struct pk_probe {          /* 24 bytes */
+    uint16_t addr;                 /* guest address of element 0 */
+    uint16_t len;                  /* bytes per element */
+    uint16_t count;                /* elements, 1..64 */
+    uint16_t stride;               /* bytes from one element to the next (ignored when count == 1) */
+    uint8_t kind, reduce, op, cmp; /* PK_PV_*, PK_PR_*, PK_PO_*, PK_PC_* */
+    uint32_t arg;                  /* the constant of cmp */
+    double weight;                 /* finite */
+} pk_probe;
+int pk_probe_create(pk_handle* h, const pk_probe* prog_host, uint32_t m);
+uint32_t pk_probe_count(const pk_handle* h);          /* 0 without a program */
+int pk_probe_eval(pk_handle* h, const uint8_t* mask_dev, uint32_t flags, uint32_t env0, uint32_t count,
+                  double* rew_dev, uint8_t* term_dev, int32_t* feat_dev, void* stream);
+
 /* Emulated instructions executed by the last pk_step, summed over envs (synchronous). */
 int pk_last_instr_count(pk_handle* h, uint64_t* out);
 

@@ -27,6 +27,12 @@ PK_COUNTS_DELTA = 1
 PK_FSTACK_CHW, PK_FSTACK_HWC = 0, 1
 PK_FSTACK_MEAN, PK_FSTACK_PICK = 0, 1
 PK_FSTACK_FILL_ONLY = 1
+PK_PV_LE, PK_PV_BE, PK_PV_BCD, PK_PV_BITS = 0, 1, 2, 3
+PK_PR_SUM, PK_PR_MAX = 0, 1
+PK_PO_NONE, PK_PO_DELTA, PK_PO_NEWMAX, PK_PO_CHANGE = 0, 1, 2, 3
+PK_PC_NONE, PK_PC_EQ, PK_PC_NE, PK_PC_GE, PK_PC_LE = 0, 1, 2, 3, 4
+PK_PROBE_REBASE_ONLY, PK_PROBE_SET = 1, 2
+PK_PROBE_MAX = 64
 HEAT_SHAPE = (444, 436)
 OBS_SHAPE = (72, 80, 4)
 # PK_ERR_* -> the exception the reference raises at that point (include/pokegym_amd.h)
@@ -53,7 +59,8 @@ EXPORTS = ("pk_create", "pk_destroy", "pk_last_error", "pk_abi_version", "pk_res
            "pk_frame_cells", "pk_frame_keys",
            "pk_counts_create", "pk_counts_limit", "pk_counts_update", "pk_counts_add", "pk_counts_pack",
            "pk_counts_read", "pk_counts_clear",
-           "pk_fstack_create", "pk_fstack_depth", "pk_fstack_scale", "pk_fstack_ptr", "pk_fstack_push")
+           "pk_fstack_create", "pk_fstack_depth", "pk_fstack_scale", "pk_fstack_ptr", "pk_fstack_push",
+           "pk_probe_create", "pk_probe_count", "pk_probe_eval")
 
 
 class PkConfig(ctypes.Structure):
@@ -83,6 +90,22 @@ class PkXrec(ctypes.Structure):
         ("payload", ctypes.c_int32),
         ("format", ctypes.c_uint32),
         ("reserved", ctypes.c_uint32 * 3),
+    ]
+
+
+class PkProbe(ctypes.Structure):
+    """pk_probe: one probe of a RAM probe program (24 bytes)."""
+    _fields_ = [
+        ("addr", ctypes.c_uint16),
+        ("len", ctypes.c_uint16),
+        ("count", ctypes.c_uint16),
+        ("stride", ctypes.c_uint16),
+        ("kind", ctypes.c_uint8),
+        ("reduce", ctypes.c_uint8),
+        ("op", ctypes.c_uint8),
+        ("cmp", ctypes.c_uint8),
+        ("arg", ctypes.c_uint32),
+        ("weight", ctypes.c_double),
     ]
 
 
@@ -142,6 +165,7 @@ def bind(L):
     bind_v12(L)
     bind_counts(L)
     bind_fstack(L)
+    bind_probes(L)
 
 
 def bind_v2(L):
@@ -268,6 +292,16 @@ def bind_fstack(L):
     L.pk_fstack_ptr.argtypes = [vp]
     L.pk_fstack_ptr.restype = vp
     L.pk_fstack_push.argtypes = [vp, vp, vp, u32, u32, u32, vp]
+
+
+def bind_probes(L):
+    """argtypes of the RAM probes (additive to ABI v12; shared with the host-simulation test build)."""
+    vp = ctypes.c_void_p
+    u32 = ctypes.c_uint32
+    L.pk_probe_create.argtypes = [vp, ctypes.POINTER(PkProbe), u32]
+    L.pk_probe_count.argtypes = [vp]
+    L.pk_probe_count.restype = u32
+    L.pk_probe_eval.argtypes = [vp, vp, u32, u32, u32, vp, vp, vp, vp]
 
 
 def check(rc: int, what: str):

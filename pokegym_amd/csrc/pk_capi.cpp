@@ -53,6 +53,7 @@ hipError_t pk_launch_cell_keys(const uint8_t* mem, uint32_t sh, uint32_t shift, 
                                uint32_t env1, hipStream_t s);
 hipError_t pk_launch_frame_keys(const PkCellArgs& a, hipStream_t s);
 hipError_t pk_launch_fstack(const PkStackArgs& a, hipStream_t s);
+hipError_t pk_launch_probe(const PkProbeArgs& a, hipStream_t s);
 hipError_t pk_launch_cnt_update(const PkCountArgs& a, hipStream_t s);
 hipError_t pk_launch_cnt_add(const PkCountArgs& a, hipStream_t s);
 hipError_t pk_launch_cnt_pack(const PkCountArgs& a, hipStream_t s);
@@ -340,6 +341,11 @@ struct pk_handle {
     // frame stack (pk_fstack_create; pk_layout.h PkStackArgs), fs_depth = 0 without one: u8[n][D * H * W]
     uint32_t fs_scale = 0, fs_depth = 0, fs_layout = 0, fs_mode = 0;
     uint8_t* fs_stack = nullptr;
+    // RAM probes (pk_probe_create; pk_layout.h PkProbeArgs), pr_m = 0 without a program: the program
+    // on the device and the state words u32[m][npad]
+    uint32_t pr_m = 0;
+    pk_probe* pr_prog = nullptr;
+    uint32_t* pr_state = nullptr;
     // profiling: 4 events per profiled step (start, after K1, after K2, after K4+K3)
     bool prof = false;
     std::vector<hipEvent_t> ev_pool;
@@ -382,7 +388,7 @@ void pk_destroy(pk_handle* h) {
                     h->b_mem, h->b_regs, h->b_lat, h->b_screen, h->b_filled, h->b_rejects, h->b_lists, h->b_src,
                     h->e_fields, h->e_seen, h->e_mask, h->e_cutc, h->b_ep_filled, h->a_fix, h->a_ones, h->a_zero,
                     h->x_fix, h->x_ones, h->x_zero, h->t_act, h->t_origin, h->t_flags, h->bt_act, h->bt_origin, h->bt_flags,
-                    h->c_fix, h->fs_stack};
+                    h->c_fix, h->fs_stack, h->pr_prog, h->pr_state};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     delete h;
@@ -1709,6 +1715,68 @@ int pk_fstack_push(pk_handle* h, const uint8_t* screen, const uint8_t* mask, uin
     a.scale = h->fs_scale; a.depth = h->fs_depth; a.layout = h->fs_layout; a.mode = h->fs_mode;
     a.fill_only = flags & PK_FSTACK_FILL_ONLY;
     HIPCHK(pk_launch_fstack(a, (hipStream_t)stream));
+    return 0;
+}
+
+// ---- RAM probes ---------------------------------------------------------------------------------
+
+uint32_t pk_probe_count(const pk_handle* h) { return h ? h->pr_m : 0; }
+
+int pk_probe_create(pk_handle* h, const pk_probe* prog, uint32_t m) {
+    if (!h || !prog) return fail(-EINVAL, "null argument");
+    if (h->pr_m) return fail(-EEXIST, "the handle already has a probe program of %u probes", h->pr_m);
+    if (m == 0 || m > PK_PROBE_MAX) return fail(-EINVAL, "a program has 1..%u probes, not %u", PK_PROBE_MAX, m);
+    for (uint32_t j = 0; j < m; j++) {
+        const pk_probe& p = prog[j];
+        if (p.kind > PK_PV_BITS) return fail(-EINVAL, "probe %u: unknown kind %u", j, p.kind);
+        if (p.reduce > PK_PR_MAX) return fail(-EINVAL, "probe %u: unknown reduce %u", j, p.reduce);
+        if (p.op > PK_PO_CHANGE) return fail(-EINVAL, "probe %u: unknown op %u", j, p.op);
+        if (p.cmp > PK_PC_LE) return fail(-EINVAL, "probe %u: unknown cmp %u", j, p.cmp);
+        const uint32_t max_len = p.kind == PK_PV_BITS ? 512u : 3u;
+        if (p.len == 0 || p.len > max_len) return fail(-EINVAL, "probe %u: len %u is outside 1..%u", j, p.len, max_len);
+        if (p.count == 0 || p.count > PK_PROBE_MAX) return fail(-EINVAL, "probe %u: count %u is outside 1..%u", j, p.count, PK_PROBE_MAX);
+        if (!(p.weight - p.weight == 0.0)) return fail(-EINVAL, "probe %u: the weight is not finite", j);
+        for (uint32_t k = 0; k < p.count; k++) {     // pk_get_ram's rule, per element
+            const uint32_t a = (uint32_t)p.addr + k * (uint32_t)p.stride, len = p.len;
+            const bool wram = a >= 0xC000 && a + len <= 0xFE00, hram = a >= 0xFF80 && a + len <= 0xFFFF;
+            if (!(wram || hram))
+                return fail(-EINVAL, "probe %u element %u: [0x%04x, +%u) is not inside WRAM/echo or HRAM", j, k, a, len);
+            if (wram && (a & 0x1FFF) + len > 0x2000)
+                return fail(-EINVAL, "probe %u element %u: [0x%04x, +%u) wraps the echo mirror", j, k, a, len);
+        }
+    }
+    HIPCHK(hipSetDevice(h->device));
+    const size_t pbytes = (size_t)m * sizeof(pk_probe), sbytes = (size_t)m * h->npad * 4;
+    pk_probe* dp = nullptr;
+    uint32_t* ds = nullptr;
+    hipError_t e = hipMalloc((void**)&dp, pbytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&ds, sbytes);
+    if (e == hipSuccess) e = hipMemcpy(dp, prog, pbytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(ds, 0, sbytes);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        if (dp) (void)hipFree(dp);
+        if (ds) (void)hipFree(ds);
+        (void)hipGetLastError();
+        return fail(-ENOMEM, "probe program of %u probes (%zu bytes of state): %s", m, sbytes, hipGetErrorString(e));
+    }
+    h->pr_prog = dp; h->pr_state = ds; h->pr_m = m;
+    return 0;
+}
+
+int pk_probe_eval(pk_handle* h, const uint8_t* mask, uint32_t flags, uint32_t env0, uint32_t count, double* rew,
+                  uint8_t* term, int32_t* feat, void* stream) {
+    int rc;
+    if ((rc = check_range(h, env0, count))) return rc;
+    if (!h->pr_m) return fail(-ENOENT, "the handle has no probe program (pk_probe_create)");
+    if (flags & ~(PK_PROBE_REBASE_ONLY | PK_PROBE_SET)) return fail(-EINVAL, "unknown flags 0x%x", flags);
+    HIPCHK(hipSetDevice(h->device));
+    PkProbeArgs a;
+    a.mem = h->mem; a.prog = h->pr_prog; a.state = h->pr_state;
+    a.mask = mask; a.rew = rew; a.term = term; a.feat = feat;
+    a.m = h->pr_m; a.npad = h->npad; a.env0 = env0; a.env1 = env0 + count; a.ilv_sh = h->ilv_sh;
+    a.rebase_only = flags & PK_PROBE_REBASE_ONLY; a.set = (flags & PK_PROBE_SET) ? 1u : 0u;
+    HIPCHK(pk_launch_probe(a, (hipStream_t)stream));
     return 0;
 }
 

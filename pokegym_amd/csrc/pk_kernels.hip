@@ -1087,6 +1087,129 @@ hipError_t pk_launch_fstack(const PkStackArgs& a, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// RAM probes (pk_probe_eval): the program's values read from every env's RAM image, turned into a
+// reward, a done flag and a feature row (include/pokegym_amd.h states the model).  Lane = env, a
+// workgroup is one wave of 64 envs, and the program is walked wave-uniformly: a byte load of the
+// wave reads runs of W = 1 << ilv_sh consecutive bytes of the interleaved image (pk_img_off), for
+// any W.  (A four-envs-per-thread instance with dword loads was measured and not kept)
+// The state words are probe-major (state[j * npad + env]), so a wave loads and stores consecutive
+// words; mask, rew and term likewise.  The feature rows i32[n][m] go through LDS, PK_PROBE_CHUNK
+// probes at a time: the tile's rows are padded by one word, and the wave then writes every env's
+// chunk as consecutive words.  No thread reads what another writes outside the tile, and there are
+// no atomics.  The barriers are reached by every thread (no early return): the host-simulation
+// build runs a workgroup as 64 threads joined at them.
+// The reward arithmetic must round every product and sum once: contraction is switched off here
+// for both compilers, the pragma of clang in the two helpers, that of gcc around the kernel.
+#if defined(__GNUC__) && !defined(__clang__)
+#pragma GCC push_options
+#pragma GCC optimize("fp-contract=off")
+#endif
+
+__device__ __forceinline__ double pk_pr_mul(double a, double b) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    return a * b;
+}
+
+__device__ __forceinline__ double pk_pr_add(double a, double b) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    return a + b;
+}
+
+// (the host-simulation build joins the threads of a workgroup at barriers only for kernels launched
+// under a PK_K1_KERNEL name)
+#define PK_K1_KERNEL_PROBE pk_probe_kernel
+__global__ void __launch_bounds__(PK_PROBE_WG) pk_probe_kernel(PkProbeArgs A) {
+    constexpr u32 C = PK_PROBE_CHUNK, LD = C + 1u;
+    __shared__ int32_t tile[PK_PROBE_WG * LD];
+    __shared__ u8 takes[PK_PROBE_WG];
+    const u32 tid = threadIdx.x, sh = A.ilv_sh;
+    const u32 base = A.env0 + blockIdx.x * PK_PROBE_WG, e = base + tid;
+    const bool in = e < A.env1, mk = in && A.mask && A.mask[e] != 0;
+    const bool part = A.rebase_only ? in && (!A.mask || mk) : in;   // part implies e < env1: the env's
+    const bool reb = A.rebase_only ? part : mk;                     // loads stay inside the images
+    takes[tid] = part;
+    const u8* img = A.mem + pk_img_off(part ? e : base, 0u, sh);
+    double r = 0.0;
+    u32 done = 0u;
+
+    for (u32 j0 = 0; j0 < A.m; j0 += C) {
+        const u32 j1 = min(j0 + C, A.m);
+        for (u32 j = j0; j < j1; j++) {
+            const pk_probe P = A.prog[j];
+            u32 v = 0u;
+            for (u32 k = 0; k < P.count; k++) {
+                const u32 a = (u32)P.addr + k * (u32)P.stride;
+                const u32 phys = a >= 0xFF80u ? PK_P_HRAM + (a - 0xFF80u) : PK_P_WRAM + (a & 0x1FFFu);
+                const u8* p = img + ((size_t)phys << sh);
+                u32 x = 0u;
+                if (P.kind == PK_PV_BITS) {
+#pragma unroll 8
+                    for (u32 b = 0; b < P.len; b++)
+                        x += (u32)__builtin_popcount(part ? (u32)p[(size_t)b << sh] : 0u);
+                } else {
+                    for (u32 b = 0; b < P.len; b++) {
+                        const u32 byte = part ? (u32)p[(size_t)b << sh] : 0u;
+                        x = P.kind == PK_PV_LE ? x | byte << (8u * b)
+                          : P.kind == PK_PV_BE ? x << 8 | byte
+                                               : x * 100u + (byte >> 4) * 10u + (byte & 15u);
+                    }
+                }
+                v = P.reduce == PK_PR_MAX ? max(v, x) : v + x;
+            }
+            if (P.op != PK_PO_NONE && part) {
+                u32* sp = A.state + (size_t)j * A.npad + e;
+                const u32 s = *sp;
+                u32 sn = v;
+                if (!reb) {
+                    double c = 0.0;
+                    if (P.op == PK_PO_DELTA) {
+                        c = pk_pr_mul(P.weight, (double)((int64_t)v - (int64_t)s));
+                    } else if (P.op == PK_PO_NEWMAX) {
+                        if (v > s) c = pk_pr_mul(P.weight, (double)(v - s));
+                        sn = max(s, v);
+                    } else if (v != s) {
+                        c = P.weight;
+                    }
+                    r = pk_pr_add(r, c);
+                }
+                *sp = sn;
+            }
+            const u32 arg = P.arg;
+            done |= P.cmp == PK_PC_EQ ? v == arg : P.cmp == PK_PC_NE ? v != arg
+                  : P.cmp == PK_PC_GE ? v >= arg : P.cmp == PK_PC_LE ? v <= arg : 0u;
+            tile[tid * LD + (j - j0)] = (int32_t)v;
+        }
+        if (A.feat) {
+            __syncthreads();
+            const u32 cols = j1 - j0;
+            for (u32 q = tid; q < PK_PROBE_WG * cols; q += PK_PROBE_WG) {
+                const u32 row = q / cols, c = q % cols;
+                if (takes[row]) A.feat[(size_t)(base + row) * A.m + j0 + c] = tile[row * LD + c];
+            }
+            __syncthreads();
+        }
+    }
+    if (part && !reb) {
+        if (A.rew) A.rew[e] = A.set ? r : pk_pr_add(A.rew[e], r);
+        if (A.term) A.term[e] = (u8)(A.set ? done : (A.term[e] | done));
+    }
+}
+
+#if defined(__GNUC__) && !defined(__clang__)
+#pragma GCC pop_options
+#endif
+
+hipError_t pk_launch_probe(const PkProbeArgs& a, hipStream_t s) {
+    const u32 count = a.env1 - a.env0;
+    hipLaunchKernelGGL(PK_K1_KERNEL_PROBE, dim3((count + PK_PROBE_WG - 1u) / PK_PROBE_WG), dim3(PK_PROBE_WG), 0, s, a);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
 // Archive exchange (pk_archive_pack / pk_archive_merge): cells as records and whole-slot payloads.
 
 // pk_archive_pack, one workgroup: the records of cells [cell0, cell0 + count) and, by a scan in cell

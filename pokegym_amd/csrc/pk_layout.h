@@ -383,3 +383,25 @@ struct PkStackArgs {
     uint32_t scale, depth, layout, mode;
     uint32_t fill_only;
 };
+
+// RAM probes (pk_probe_*): the program is the caller's pk_probe table (24 bytes a probe, at most 64)
+// copied to the device once its elements are validated; the guest address of an element becomes a
+// phys address in the kernel by two wave-uniform operations (the elements of one probe may lie in
+// WRAM, its echo and HRAM).  The per-env state is one word per probe, probe-major:
+// state[j * npad + env], so that a wave's loads and stores of a probe's state are consecutive words.
+#define PK_PROBE_WG 64u
+#define PK_PROBE_CHUNK 16u       // probes per pass of the feature tile in LDS
+
+struct PkProbeArgs {
+    const uint8_t* mem;          // lane-interleaved RAM images
+    const struct pk_probe* prog; // [m], device
+    uint32_t* state;             // [m][npad]
+    const uint8_t* mask;         // caller's [n] or null
+    double* rew;                 // caller's [n] or null
+    uint8_t* term;               // caller's [n] or null
+    int32_t* feat;               // caller's [n][m] or null
+    uint32_t m, npad;
+    uint32_t env0, env1;
+    uint32_t ilv_sh;
+    uint32_t rebase_only, set;
+};

@@ -529,6 +529,45 @@ class BatchedEmulator:
               "pk_fstack_push")
         return self.stack
 
+    # -- RAM probes (stream-ordered except create) -----------------------------------------
+    def probes_create(self, program):
+        """Give the handle a probe program: a list of probes.Probe records (pk_probe_create; once,
+        synchronous; any handle).  A program the header's rules reject raises ValueError."""
+        from . import probes
+        try:
+            arr = probes.pack(program)
+        except TypeError as e:
+            raise ValueError(str(e)) from None
+        check(self._L.pk_probe_create(self._h, arr, len(arr)), "pk_probe_create")
+        self.probe_program = list(program)
+
+    @property
+    def probe_count(self) -> int:
+        """The probes of the handle's program (pk_probe_count); 0 without probes_create."""
+        return int(self._L.pk_probe_count(self._h))
+
+    def probes_eval(self, mask: torch.Tensor | None = None, rebase_only: bool = False, set: bool = False,
+                    rewards: torch.Tensor | None = None, terminals: torch.Tensor | None = None,
+                    features: torch.Tensor | None = None, env0: int = 0, count: int | None = None):
+        """Evaluate the program for the envs of the range in one launch (pk_probe_eval, on the current
+        stream).  mask: a full-size uint8 (n,) tensor; an env with mask[e] != 0 rebases — its state
+        takes the current values, its outputs stay — the others evaluate: rewards[e] += r and
+        terminals[e] |= done, or = with set=True.  rebase_only=True touches only the envs with
+        mask[e] != 0 (no mask: the whole range) and rebases them.  rewards float64 (n,), terminals
+        uint8 (n,) and features int32 (n, m) are full-size tensors on the device, each optional;
+        features takes the values of every env that took part."""
+        count = self.n - env0 if count is None else count
+        fp = None
+        if features is not None:
+            if (features.dtype != torch.int32 or features.device != self.device or not features.is_contiguous()
+                    or tuple(features.shape) != (self.n, self.probe_count)):
+                raise ValueError("features must be a contiguous int32 (n_envs, probe_count) tensor on the emulator's device")
+            fp = ctypes.c_void_p(features.data_ptr())
+        flags = (_native.PK_PROBE_REBASE_ONLY if rebase_only else 0) | (_native.PK_PROBE_SET if set else 0)
+        check(self._L.pk_probe_eval(self._h, self._full(mask, torch.uint8, "mask"), flags, env0, count,
+                                    self._full(rewards, torch.float64, "rewards"),
+                                    self._full(terminals, torch.uint8, "terminals"), fp, self._stream()), "pk_probe_eval")
+
     # -- action trajectories (stream-ordered except enable) -------------------------------
     def traj_enable(self):
         """Record every env's actions from here on (pk_traj_enable; once, synchronous).  Call it

@@ -266,10 +266,11 @@ class VecEnv:
                  record_trajectories: bool = False, archive_exchange: bool = False, archive_key: str = "ram",
                  archive_frame=(16, 16, 8), novelty_log2: int = 0, novelty_beta: float = 1.0, novelty_key: str = "frame",
                  novelty_frame=(16, 16, 8), frame_stack: int = 0, stack_scale: int = 2, stack_layout: str = "chw",
-                 stack_mode: str = "mean"):
-        """reward=False: the screen-obs env of configs[3] — obs is the (144, 160) u8 screen, rewards are
-        0 and episodes end at max_episode_steps.  power_on=True starts (and resets) every env from
-        the cartridge's power-on state instead of a savestate.
+                 stack_mode: str = "mean", probes=None, probe_features: bool = False):
+        """reward=False: the screen-obs env of configs[3] — obs is the (144, 160) u8 screen; without
+        probes= or novelty_log2= the rewards are 0 and episodes end at max_episode_steps.
+        power_on=True starts (and resets) every env from the cartridge's power-on state instead of
+        a savestate.
 
         state_pool (a list of v9 savestates, bytes or paths) puts the states into a device savestate
         bank; every reset, the auto-resets included, then starts each env from a slot drawn on the
@@ -331,7 +332,22 @@ class VecEnv:
         the first frame of its next episode.  reset() fills every env, and load_from_bank,
         resume_from_bank, fork, archive_explore and load_state refill the envs whose machine they
         replaced (load_from_bank: every env it names with a slot of the bank).  With 0 nothing is
-        allocated or launched."""
+        allocated or launched.
+
+        probes=program (a list of probes.Probe records, e.g. probes.pkbench_program(); None = off) reads a
+        reward and a termination condition from every env's RAM (pk_probe_*), on any cartridge: with
+        reward=False they are the env's reward and the only way an episode ends before
+        max_episode_steps, with reward=True they are added on top of the reward stack's.  Right after
+        each sub-batch's step, on its stream, one launch adds the program's reward into the emulator's
+        reward array and ORs its done flag into the terminal array, so the returned rewards and
+        terminals, the episode statistics and the auto-reset all see them; a second launch after the
+        auto-reset rebases the envs that were reset, so their next step is measured from the reset
+        state.  reset() rebases every env, and load_from_bank, resume_from_bank, fork, archive_explore
+        and load_state rebase the envs whose machine they replaced, at the sites and with the masks of
+        the frame stack's refill: the probe state does not travel through the bank, a resumed
+        "newmax" starts again from the current value.  probe_features=True also keeps the probe values:
+        probe_values is int32 (num_envs, m), the values every env's last step ended on (probe_space).
+        With None nothing is allocated or launched."""
         self.batch_size = batch_size or num_envs
         if num_envs % self.batch_size:
             raise ValueError("batch_size must divide num_envs")
@@ -370,6 +386,18 @@ class VecEnv:
             if not getattr(emulator, "render", True):
                 raise ValueError("frame_stack needs an emulator that renders (render=True)")
             self.emu.stack_create(stack_scale, frame_stack, stack_layout, stack_mode)
+        # RAM probes (pk_probe_*): nothing is allocated or called with probes=None
+        self.probes = None if probes is None else list(probes)
+        self._probe_feat = None
+        self.probe_space = None
+        if self.probes is None:
+            if probe_features:
+                raise ValueError("probe_features=True needs probes=")
+        else:
+            self.emu.probes_create(self.probes)
+            self.probe_space = spaces.probe_space(len(self.probes))
+            if probe_features:
+                self._probe_feat = torch.zeros((n_phys, len(self.probes)), dtype=torch.int32, device=self.device)
         self.single_action_space = spaces.action_space()
         self.env_ids = torch.arange(env_offset, env_offset + num_envs, device=self.device)
         self.masks = torch.ones(num_envs, dtype=torch.bool, device=self.device)
@@ -526,8 +554,16 @@ class VecEnv:
         self._join_streams()
         m = self._bank_map(envs, slots)
         self.emu.bank_load(m)
+        if self.frame_stack or self.probes is not None:
+            self._machines_replaced(((m >= 0) & (m < self.emu.bank_slots)).to(torch.uint8))
+
+    def _machines_replaced(self, mask: torch.Tensor):
+        """The envs with mask[e] != 0 (uint8, emulator order) run another machine from here on: their
+        frame stacks start over and their probes are rebased, on the current stream."""
         if self.frame_stack:
-            self.emu.stack_push(((m >= 0) & (m < self.emu.bank_slots)).to(torch.uint8), fill_only=True)
+            self.emu.stack_push(mask, fill_only=True)
+        if self.probes is not None:
+            self.emu.probes_eval(mask, rebase_only=True, features=self._probe_feat)
 
     def _episode_args(self, envs, slots):
         if self._ck_return is None:
@@ -575,10 +611,10 @@ class VecEnv:
         phys = (envs // self.batch_size) * self.slot + envs % self.batch_size
         if self._slots is not None:
             self._slots[phys] = torch.where(ok, self._ck_slots[slots], self._slots[phys])
-        if self.frame_stack:                 # the resumed envs start a history of their own
+        if self.frame_stack or self.probes is not None:   # the resumed envs start a history of their own
             m = torch.zeros(self.emu.n, dtype=torch.uint8, device=self.device)
             m[phys] = ok.to(torch.uint8)
-            self.emu.stack_push(m, fill_only=True)
+            self._machines_replaced(m)
 
     def fork(self, dst_envs, src_envs, check: bool = True):
         """Copy the running episode of env src_envs[i] over env dst_envs[i]: every distinct source
@@ -675,8 +711,8 @@ class VecEnv:
         self._join_streams()
         mask = self._physical(torch.as_tensor(mask, device=self.device) != 0, 0, torch.uint8)
         self.emu.archive_explore(mask, out=self._arch_out)
-        if self.frame_stack:                 # the envs that resumed: the device's own answer, rejects excluded
-            self.emu.stack_push((self._arch_out >= 0).to(torch.uint8), fill_only=True)
+        if self.frame_stack or self.probes is not None:   # the envs that resumed: the device's own answer, rejects excluded
+            self._machines_replaced((self._arch_out >= 0).to(torch.uint8))
         drawn = self._logical(self._arch_out).long()
         last = self._ck_return.numel() - 1
         slots = torch.where(drawn >= 0, drawn, last)
@@ -859,6 +895,8 @@ class VecEnv:
             obs = self._logical(self.emu.reset_from(self._slots))
         if self.frame_stack:
             obs = self._logical(self.emu.stack_push(fill_only=True))
+        if self.probes is not None:
+            self.emu.probes_eval(rebase_only=True, features=self._probe_feat)
         self.t = 0
         self._log_wait = 0
         if self.sticky_errors is not None:
@@ -959,6 +997,9 @@ class VecEnv:
             obs, rew, term, trunc = self.emu.step(actions)
         else:
             obs, rew, term, trunc = self.emu.step_range(psl.start, actions)
+        if self.probes is not None:     # rew and term are views of the arrays this adds and ORs into
+            self.emu.probes_eval(rewards=self.emu.rewards, terminals=self.emu.terminals, features=self._probe_feat,
+                                 env0=psl.start, count=self.batch_size)
         self.stats.update(rew, term, batch=b, envs=sl)
         if self.info_stats is not None:
             self.info_stats.update(self.emu.info[:, psl], self.emu.info_flag[psl], batch=b)
@@ -986,6 +1027,8 @@ class VecEnv:
             self.emu.reset(term)
         else:
             self.emu.reset_range(psl.start, self.batch_size, self.emu.terminals)
+        if self.probes is not None:  # the finished envs are measured from their reset state; the features stay the step's
+            self.emu.probes_eval(self.emu.terminals, rebase_only=True, env0=psl.start, count=self.batch_size)
         if self.frame_stack:        # one launch: the finished envs fill from their reset frame, the others push
             obs = self.emu.stack_push(self.emu.terminals, env0=psl.start, count=self.batch_size)[psl]
         return obs, rewards, terminals, truncations
@@ -1067,11 +1110,20 @@ class VecEnv:
     def load_state(self, env: int, state: bytes):
         """Install a v9 savestate into one env (pk_load_env; pyboy_binding.py:59-69)."""
         self.emu.load_env(self.phys(env), state)
-        if self.frame_stack:
+        if self.frame_stack or self.probes is not None:
             self._join_streams()
             m = torch.zeros(self.emu.n, dtype=torch.uint8, device=self.device)
             m[self.phys(env)] = 1
-            self.emu.stack_push(m, fill_only=True)
+            self._machines_replaced(m)
+
+    @property
+    def probe_values(self) -> torch.Tensor:
+        """The probe values every env's last step ended on, or its last reset or rebase produced (int32
+        (num_envs, m), env order); needs probes= and probe_features=True."""
+        if self._probe_feat is None:
+            raise RuntimeError("VecEnv(probes=..., probe_features=True) keeps the probe values")
+        self._join_streams()
+        return self._logical(self._probe_feat).clone()
 
     def video_recorder(self, envs, capacity: int = 1024):
         """A FrameRecorder (pokegym_amd/video.py) of the given envs' screens: call .capture() after

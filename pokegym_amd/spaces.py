@@ -65,3 +65,10 @@ def stack_space(scale: int = 2, depth: int = 4, layout: str = "chw"):
     """The frame stack VecEnv(frame_stack=depth) returns: depth downscaled frames, newest first —
     (depth, 144 / scale, 160 / scale) for "chw", (144 / scale, 160 / scale, depth) for "hwc"."""
     return Box(low=0, high=255, shape=stack_shape(scale, depth, layout), dtype=np.uint8)
+
+
+def probe_space(m: int):
+    """The feature vector of a RAM probe program of m probes (VecEnv.probe_values): m values below 2**30."""
+    if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 1 <= m <= 64:
+        raise ValueError("a probe program has 1..64 probes")
+    return Box(low=0, high=(1 << 30) - 1, shape=(int(m),), dtype=np.int32)
