@@ -249,6 +249,23 @@ __device__ __forceinline__ u32 rom_lds_index(const St& s, u32 a) { return a + se
 __device__ __forceinline__ u32 rom_global_index(const PkStepArgs& A, const St& s, u32 a) {
     return (((s.mbc & 0xFFu) & A.rom_bank_mask) << 14) | (a & 0x3FFFu);
 }
+// pav: what the fused-pair decision needs to know about where the code at pc lives, carried with
+// the fetched bytes (the stage that fetches them has classified pc already) instead of re-derived
+// from pc in every iteration.  Bits 0-2: the fetched bytes a pair may take — up to 4 for ROM code,
+// fewer at the end of its 16 KiB bank (the LDS slots of other banks follow it), 3 for code in RAM
+// (what every fetch path provides), 0 where the bytes would reach the IO registers (0xFEFE-0xFF7F:
+// DIV and a folded STAT change with the clock).  Bit 4 (PK_PAV_ROM, the D word's write bit): ROM
+// code, which a write cannot change.  RAM code may fuse only after a primary that writes nothing
+// (the fetched bytes stay valid): pav | nwv has bit 4 set exactly when the pair's bytes are safe,
+// so the bytes left after the primary are the saturating (pav | nwv) - (len | PK_PAV_ROM).
+#define PK_PAV_ROM (1u << PK_DB_WR)
+__device__ __forceinline__ u32 pav_at(u32 pc) {
+    return sel(pc < 0x8000u, min(4u, 0x4000u - (pc & 0x3FFFu)) | PK_PAV_ROM, sel(pc - 0xFEFEu < 0x82u, 0u, 3u));
+}
+// a prefetched pc is at least PK_PF_TAIL bytes before its bank's end (a pc nearer to it refetches
+// at the loop top): a prefetched ROM instruction always has 4 bytes, so the prefetch stage's pav
+// is one select of two constants
+#define PK_PF_TAIL 4u
 // The clock the next LCD event (LCD on) or the LCD-off frame end happens at, or 0 while the timer
 // runs: clock + cycles < lim is "the timer/LCD stage has nothing to do" (fused pairs, the common
 // tick).  Kept in St.lim and recomputed wherever target, LCDC, TAC, the clock or the watchdog
@@ -670,6 +687,7 @@ struct Mc {   // a microcode entry (pk_ucode.h), one VGPR per word
 };
 struct Ex {   // what the rest of the iteration needs from the instruction
     u32 addr0, addr1, o0, o1, wv0, wv1, cycles;
+    u32 nwv;                    // PK_PAV_ROM's bit when the instruction writes nothing, else 0 (!wr as a value)
     bool wr, wr2, wram, slow;   // slow: a write the generic bus path takes (wr & !wram)
 };
 template <bool PRIO, bool ALL>
@@ -835,7 +853,8 @@ __device__ __forceinline__ void pk_exec(St& s, const Ctx& c, u32 pc, u32 bytes, 
 
     // the write: wv0 at addr0, wv1 at addr1 (16-bit writes: low byte first in memory; pushes
     // SP-2, SP-1); the stage itself (pk_write) runs after the secondary op
-    x.wr = (D & tkm & (1u << PK_DB_WR)) != 0u;
+    x.nwv = ~(D & tkm) & (1u << PK_DB_WR);
+    x.wr = x.nwv == 0u;
     x.wr2 = bit(D, PK_DB_WR2) != 0u;
     x.wram = x.wr & fast01;
     x.slow = x.wr & !fast01;
@@ -946,8 +965,8 @@ __device__ __forceinline__ void pk_write(St& s, const Ctx& c, u32 env, const Mc&
 //   * the HRAM code mirror == the image's bytes 0xFF80-0xFF9F;
 //   * prefetched bytes (pbytes != PK_COPY_W0) == the bytes the bus holds at pc (the ones any use can
 //     take: up to the bank end for ROM code, 3 for code in RAM) and p0..p3 == their microcode entry.
-static __device__ void pk_check_lane(const St& s, const Ctx& c, int slack, u32 pbytes, const uint4& p0, const uint4& p1,
-                              const uint4& p2, const uint4& p3) {
+static __device__ void pk_check_lane(const St& s, const Ctx& c, int slack, u32 pbytes, u32 pav, const uint4& p0,
+                              const uint4& p1, const uint4& p2, const uint4& p3) {
     const u32 env = c.env, cpu = s.cpu;
     PK_CHECK(env, ((cpu & CPU_PEND) != 0u) == (((cpu >> 8) & (cpu >> 16) & 0x1Fu) != 0u), "CPU_PEND != IE & IF");
     PK_CHECK(env, !(cpu & CPU_HALT) || s.lim == 0u, "halted with lim != 0");
@@ -962,6 +981,10 @@ static __device__ void pk_check_lane(const St& s, const Ctx& c, int slack, u32 p
     if (pbytes != PK_COPY_W0) {
         const u32 pc = s.pc;
         const u32 nb = pc < 0x8000u ? min(4u, 0x4000u - (pc & 0x3FFFu)) : 3u;
+        // pav, recomputed from pc without pav_at: the pair's bytes and the ROM bit
+        const bool iorow = pc >= 0xFEFEu && pc <= 0xFF7Fu;
+        PK_CHECK(env, pav == (pc < 0x8000u ? (nb | PK_PAV_ROM) : iorow ? 0u : 3u), "pav != the pair bytes at pc");
+        PK_CHECK(env, pc >= 0x8000u || nb == 4u, "prefetched ROM code within PK_PF_TAIL of its bank end");
         for (u32 k = 0; k < nb; k++)
             PK_CHECK(env, ((pbytes >> (8u * k)) & 0xFFu) == bus_read_any(c, s, (pc + k) & 0xFFFFu), "prefetched bytes stale");
         const u32 op = pbytes & 0xFFu;
@@ -1100,6 +1123,7 @@ __global__ void __launch_bounds__(PK_K1_MAX_THREADS) PK_K1_KERNEL(PkStepArgs A) 
     // decode at the top instead (the block-copy loop's own first bytes, which take the rare loop-top
     // stage anyway, are fetched there again), so the loop top tests one value for both
     u32 pbytes = PK_COPY_W0;
+    u32 ppav = 0;   // pav of the prefetched pc (a lane that refetches at the loop top computes its own)
     uint4 p0 = make_uint4(0, 0, 0, 0), p1 = p0, p2 = p0, p3 = p0;
 #ifdef PK_STAMP
     uint64_t st_acc[PK_NSTAMP] = {}, st_prev = __builtin_amdgcn_s_memtime(), st_iter = 0;
@@ -1107,7 +1131,7 @@ __global__ void __launch_bounds__(PK_K1_MAX_THREADS) PK_K1_KERNEL(PkStepArgs A) 
     while (frame < A.frames) {
         u32 ev = 0;
 #if PK_CHECK_ON
-        pk_check_lane(s, c, slack, pbytes, p0, p1, p2, p3);
+        pk_check_lane(s, c, slack, pbytes, ppav, p0, p1, p2, p3);
 #endif
 #ifdef PK_WAVETIME
         wt_iter++;
@@ -1121,7 +1145,7 @@ __global__ void __launch_bounds__(PK_K1_MAX_THREADS) PK_K1_KERNEL(PkStepArgs A) 
         const u32 cpu0 = s.cpu;
         bool exec = true, doint = false, dispatch = false;
         u32 pc = s.pc, intflag = 0;
-        u32 bytes = pbytes;
+        u32 bytes = pbytes, pav = ppav;
         uint4 e0 = p0, e1 = p1, e2 = p2, e3 = p3;
         // the three rare stages of the loop top (interrupts / HALT, a fetch that was not prefetched,
         // a block-copy or LY-poll loop at pc) sit behind one test: the common path pays one branch
@@ -1149,6 +1173,7 @@ __global__ void __launch_bounds__(PK_K1_MAX_THREADS) PK_K1_KERNEL(PkStepArgs A) 
         // ---------------- fetch + microcode entry (prefetched, or here when pf = false) ----------------
         if (!pf) {
             PK_STAMP_AT(8);
+            pav = pav_at(pc);
             const bool flds = rom_staged(s, pc) && (pc & 0x3FFFu) < 0x3FFEu;
             const u32 la = sel(flds, rom_lds_index(s, pc), 0u);
             bytes = __builtin_amdgcn_alignbyte(romw[(la >> 2) + 1u], romw[la >> 2], la & 3u);
@@ -1223,7 +1248,7 @@ __global__ void __launch_bounds__(PK_K1_MAX_THREADS) PK_K1_KERNEL(PkStepArgs A) 
         Ex x;
         pk_exec<PRIO, ALL>(s, c, pc, bytes, m, ev, x PK_STAMP_ARGS);
         u32 cycles = x.cycles;
-        const bool wr = x.wr, slow = x.slow;
+        const bool slow = x.slow;
         // ---------------- fused secondary op (pk_ucode.h pk_u2_entry) ----------------
         // The instruction after this one, if it is a JR (cc), LD r,r', INC/DEC r, INC/DEC BC/DE/HL or
         // NOP, runs in this iteration on the registers and flags just written, as PyBoy's next
@@ -1236,16 +1261,16 @@ __global__ void __launch_bounds__(PK_K1_MAX_THREADS) PK_K1_KERNEL(PkStepArgs A) 
         // (ROM code has 4), and none of them an IO register (DIV and a folded STAT change with the clock).
         {
             const u32 len2 = u2.y & 3u;
-            // a secondary op (len2 != 0) and both instructions within the fetched bytes,
-            // (D & 3) + len2 <= avail: 4 for ROM code (and inside its 16 KiB bank: the LDS slots of
-            // other banks follow it), 3 for code in RAM.  As one compare: len2 - 1 wraps for len2 = 0,
-            // and avail - (D & 3) saturates (v_sub clamp) for an instruction at the bank end
-            const u32 avail = sel(pc < 0x8000u, min(4u, 0x4000u - (pc & 0x3FFFu)), 3u);
-            const bool lenok = len2 - 1u < (avail > (D & 3u) ? avail - (D & 3u) : 0u);
-            const bool ramok = (pc < 0x8000u) | (!wr & !(pc - 0xFEFEu < 0x82u));
+            // a secondary op (len2 != 0) and both instructions within the bytes a pair may take at
+            // this pc, (D & 3) + len2 <= pav's count, and, for code in RAM, no write (pav above: the
+            // stage that fetched the bytes classified pc).  As one compare: len2 - 1 wraps for
+            // len2 = 0, and the subtraction saturates (v_sub clamp) for an instruction at the bank
+            // end, for RAM code after a write (bit 4 missing) and next to the IO registers (count 0)
+            const u32 have = pav | x.nwv, need = (D & 3u) | PK_PAV_ROM;
+            const bool lenok = len2 - 1u < (have > need ? have - need : 0u);
             // next LCD event / LCD-off frame end, 0 with the timer on (tick_lim)
             // (s.lim also bounds the watchdog: clock + cycles < lim implies cycles < slack)
-            const bool fuse = (s.clock + cycles < s.lim) & !slow & ramok & lenok;
+            const bool fuse = (s.clock + cycles < s.lim) & !slow & lenok;
             const u32 M2 = sel(fuse, u2.y, PK_U2_NONE_Y);
             // X (pair, or register in byte 0); Y = register | immediate n, ^ the subtract mask, + delta;
             // one adder X + Y + carry-in (ADC/SBC: F.C; SUB/SBC/CP: ^ 1), a logic unit (AND XOR OR),
@@ -1277,7 +1302,7 @@ __global__ void __launch_bounds__(PK_K1_MAX_THREADS) PK_K1_KERNEL(PkStepArgs A) 
             ev |= sel(fuse, PK_EV_FUSE, 0u);
 #ifdef PK_DBG_FUSE
             ev |= sel(len2 != 0u, 1u << 23, 0u) | sel((int)cycles < slack, 1u << 24, 0u) | sel(s.clock + cycles < s.lim, 1u << 25, 0u)
-                | sel(!slow & ramok, 1u << 27, 0u);
+                | sel(!slow & ((have & PK_PAV_ROM) != 0u), 1u << 27, 0u);
 #endif
             s.w0 = w0f;
             s.w1 = w1f;
@@ -1299,7 +1324,7 @@ __global__ void __launch_bounds__(PK_K1_MAX_THREADS) PK_K1_KERNEL(PkStepArgs A) 
         // global-ROM dwords are requested now, so their latency overlaps the write stage (a lane
         // whose write switches the ROM bank refetches at the top of the next iteration)
         u32 ng0 = PK_UNREAD(u2b.x), ng1 = PK_UNREAD(u2b.y), nga = PK_UNREAD(u2b.z);   // read only where loaded (fg)
-        const bool nfg = !ALL & !rom_staged(s, s.pc) & (s.pc - 0x4000u < 0x3FFEu)
+        const bool nfg = !ALL & !rom_staged(s, s.pc) & (s.pc - 0x4000u <= 0x4000u - PK_PF_TAIL)
                        & !(s.pc - 0xFF80u < 0x7Du);
         if (nfg) {
             nga = rom_global_index(A, s, s.pc);
@@ -1318,7 +1343,7 @@ __global__ void __launch_bounds__(PK_K1_MAX_THREADS) PK_K1_KERNEL(PkStepArgs A) 
         if constexpr (PRIO) __builtin_amdgcn_s_setprio(3);
         {
             const u32 npc = s.pc;
-            const bool fl = (ALL ? npc < 0x8000u : rom_staged(s, npc)) && (npc & 0x3FFFu) < 0x3FFEu;
+            const bool fl = (ALL ? npc < 0x8000u : rom_staged(s, npc)) && (npc & 0x3FFFu) <= 0x4000u - PK_PF_TAIL;
             // staged ROM or the HRAM code mirror: one LDS byte index, one ds_read2_b32
             const bool fh = npc - 0xFF80u < PK_HC_ROWS - 2u;
             const u32 la = sel(fh, PK_HC_BASE + c.loc * PK_HC_STRIDE + (npc - 0xFF80u), sel(fl, rom_lds_index(s, npc), 0u));
@@ -1339,6 +1364,7 @@ __global__ void __launch_bounds__(PK_K1_MAX_THREADS) PK_K1_KERNEL(PkStepArgs A) 
             p2 = ucv[di * 4u + 2u];
             p3 = ucv[di * 4u + 3u];
             pbytes = sel(fl | fh | fg, pbytes, PK_COPY_W0);
+            ppav = sel(fh, 3u, 4u | PK_PAV_ROM);   // (fl, fg: ROM code PK_PF_TAIL before its bank end)
         }
 
 
