@@ -268,6 +268,45 @@ int pk_bank_enable_episodes(pk_handle* h);
 int pk_bank_has_episodes(const pk_handle* h);
 int pk_bank_checkpoint(pk_handle* h, const int32_t* slot_of_env_dev, uint32_t env0, uint32_t count, void* stream);
 int pk_bank_resume(pk_handle* h, const int32_t* slot_of_env_dev, uint32_t env0, uint32_t count, void* stream);
+/* Generic episode parts: checkpoints, resumes and the archive on a handle WITHOUT PK_F_REWARD, so on
+ * any cartridge.  pk_bank_enable_episodes keeps refusing such a handle; this call gives its slots a
+ * second kind of episode part, which carries what an episode consists of there:
+ *   - every lane register raw (the step counter, the held buttons and window line, the CPU bits the
+ *     machine part normalises), always;
+ *   - PK_GEP_PROBES: the env's probe state words, so a resumed PK_PO_NEWMAX keeps its maximum and a
+ *     resumed PK_PO_DELTA is measured from the checkpoint's value;
+ *   - PK_GEP_STACK: the env's row of the frame stack, so a resumed policy sees the checkpoint's frames.
+ * An env resumed from such a slot and fed the same actions produces the screens, machine states,
+ * termination flags, probe rewards and features and stack rows of the env it was saved from, bit for
+ * bit.  A part that was not asked for stays the destination env's, as before.
+ *
+ * Memory per slot, every part 16-byte aligned: 80 bytes of registers, 4 * (m rounded up to 4) bytes
+ * with PK_GEP_PROBES, depth * H * W bytes with PK_GEP_STACK, besides the machine part.
+ *
+ * pk_bank_enable_generic_episodes (synchronous): once per handle; needs a bank, a handle without
+ * PK_F_REWARD and, for each part asked for, the feature itself (pk_probe_create / pk_fstack_create
+ * first).  On failure — PK_F_REWARD set, no bank, an unknown bit in parts, a part whose feature is
+ * missing, a second call, out of memory — the handle is unchanged and a later correct call succeeds.
+ * pk_bank_generic_parts: parts | 0x80000000 once enabled, else 0.  pk_bank_generic_episode_bytes: the
+ * bytes per slot stated above, 0 without.  A handle that never calls it makes exactly the launches
+ * and allocations it made before.
+ *
+ * After it pk_bank_has_episodes is 1, and pk_bank_checkpoint / pk_bank_resume run the list and
+ * validation and the machine part's kernels as on a reward handle, then one mover for the generic
+ * part and, with trajectories, the trajectory mover; there is no observation to rebuild.  Reject
+ * rules, the reject counter, ordering and concurrency are unchanged: a rejected env is untouched in
+ * every part, many envs may resume from one slot, pk_bank_put and pk_bank_save leave a slot's episode
+ * part empty.  pk_traj_enable works before or after the call.  pk_set_episode_params never empties
+ * generic parts (their size does not depend on the episode length); when it reallocates the
+ * trajectory rows, the slots' rows are flagged PK_TRAJ_BROKEN.  pk_archive_create, _update, _explore
+ * and _read work on top, with any keys (pk_frame_keys) and scores (accumulated probe reward).
+ * pk_archive_exchange_enable fails with a negative code on such a handle and changes nothing: the
+ * exchange payload has no format for generic parts. */
+#define PK_GEP_PROBES 1u   /* carry the probe state words (needs pk_probe_create first) */
+#define PK_GEP_STACK 2u    /* carry the frame stack planes (needs pk_fstack_create first) */
+int pk_bank_enable_generic_episodes(pk_handle* h, uint32_t parts);
+uint32_t pk_bank_generic_parts(const pk_handle* h);          /* parts | 0x80000000 once enabled, else 0 */
+uint64_t pk_bank_generic_episode_bytes(const pk_handle* h);  /* bytes per slot of the generic part, 0 without */
 /* Envs rejected by pk_bank_save / pk_bank_load / pk_reset_from / pk_bank_checkpoint /
  * pk_bank_resume since the last call; clears the counter (synchronous). */
 int pk_bank_rejects(pk_handle* h, uint64_t* out);
@@ -451,7 +490,8 @@ int pk_bank_traj_get(pk_handle* h, uint32_t slot0, uint32_t count, int32_t* orig
  * a slot of the SOURCE's bank, so keeping the state pools of exchanging handles identical is the
  * caller's job.
  *
- * pk_archive_exchange_enable (synchronous): once per handle, needs an archive.  It allocates three
+ * pk_archive_exchange_enable (synchronous): once per handle, needs an archive whose slots carry the
+ * reward stack's episode parts (generic episode parts have no payload format: -ENOTSUP).  It allocates three
  * words per cell (sent_visits, sent_picks, dirty; all 0) and the scratch of pk_archive_merge, which
  * therefore never allocates for up to 65,536 records.  On failure the handle is unchanged.  A
  * handle that never calls it makes exactly the launches and allocations it made before; on it
@@ -625,9 +665,11 @@ int pk_counts_clear(pk_handle* h, void* stream);
  * screen pointer, a range past n, an env0 that is no multiple of 64) are a negative code with
  * pk_last_error, never a fault, and write nothing.
  *
- * A stack belongs to the env, not to the episode or the machine: bank slots, checkpoints, the
- * archive and the exchange payload do not carry it and keep their formats.  The caller refills
- * (PK_FSTACK_FILL_ONLY) an env whose machine was replaced; VecEnv(frame_stack=D) does. */
+ * A stack row is carried by generic episode parts when requested (PK_GEP_STACK: checkpoints,
+ * resumes and the archive of a handle without PK_F_REWARD).  Otherwise it belongs to the env, not to
+ * the episode or the machine: bank slots, checkpoints, the archive and the exchange payload do not
+ * carry it and keep their formats, and the caller refills (PK_FSTACK_FILL_ONLY) an env whose
+ * machine was replaced; VecEnv(frame_stack=D) does. */
 #define PK_FSTACK_CHW 0u        /* u8[n][depth][H][W] */
 #define PK_FSTACK_HWC 1u        /* u8[n][H][W][depth] */
 #define PK_FSTACK_MEAN 0u
@@ -693,8 +735,10 @@ int pk_fstack_push(pk_handle* h, const uint8_t* screen_dev, const uint8_t* mask_
  * an env0 that is no multiple of 64) are a negative code with pk_last_error, never a fault, and write
  * nothing.
  *
- * The state belongs to the env, as the frame stack does: bank slots, checkpoints, the archive and
- * the exchange payload do not carry it and keep their formats.  The caller rebases
+ * The state is carried by generic episode parts when requested (PK_GEP_PROBES: checkpoints, resumes
+ * and the archive of a handle without PK_F_REWARD; a resumed PK_PO_NEWMAX then keeps its maximum).
+ * Otherwise it belongs to the env, as the frame stack does: bank slots, checkpoints, the archive and
+ * the exchange payload do not carry it and keep their formats, and the caller rebases
  * (PK_PROBE_REBASE_ONLY) an env whose machine was replaced — a reset, a load, a resume — so a resumed
  * PK_PO_NEWMAX starts again from the current value; VecEnv(probes=...) does. */
 #define PK_PV_LE 0u

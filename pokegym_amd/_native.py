@@ -33,6 +33,7 @@ PK_PO_NONE, PK_PO_DELTA, PK_PO_NEWMAX, PK_PO_CHANGE = 0, 1, 2, 3
 PK_PC_NONE, PK_PC_EQ, PK_PC_NE, PK_PC_GE, PK_PC_LE = 0, 1, 2, 3, 4
 PK_PROBE_REBASE_ONLY, PK_PROBE_SET = 1, 2
 PK_PROBE_MAX = 64
+PK_GEP_PROBES, PK_GEP_STACK = 1, 2
 HEAT_SHAPE = (444, 436)
 OBS_SHAPE = (72, 80, 4)
 # PK_ERR_* -> the exception the reference raises at that point (include/pokegym_amd.h)
@@ -60,7 +61,8 @@ EXPORTS = ("pk_create", "pk_destroy", "pk_last_error", "pk_abi_version", "pk_res
            "pk_counts_create", "pk_counts_limit", "pk_counts_update", "pk_counts_add", "pk_counts_pack",
            "pk_counts_read", "pk_counts_clear",
            "pk_fstack_create", "pk_fstack_depth", "pk_fstack_scale", "pk_fstack_ptr", "pk_fstack_push",
-           "pk_probe_create", "pk_probe_count", "pk_probe_eval")
+           "pk_probe_create", "pk_probe_count", "pk_probe_eval",
+           "pk_bank_enable_generic_episodes", "pk_bank_generic_parts", "pk_bank_generic_episode_bytes")
 
 
 class PkConfig(ctypes.Structure):
@@ -166,6 +168,7 @@ def bind(L):
     bind_counts(L)
     bind_fstack(L)
     bind_probes(L)
+    bind_generic(L)
 
 
 def bind_v2(L):
@@ -302,6 +305,16 @@ def bind_probes(L):
     L.pk_probe_count.argtypes = [vp]
     L.pk_probe_count.restype = u32
     L.pk_probe_eval.argtypes = [vp, vp, u32, u32, u32, vp, vp, vp, vp]
+
+
+def bind_generic(L):
+    """argtypes of the generic episode parts (additive to ABI v12; shared with the host-simulation test build)."""
+    vp = ctypes.c_void_p
+    L.pk_bank_enable_generic_episodes.argtypes = [vp, ctypes.c_uint32]
+    L.pk_bank_generic_parts.argtypes = [vp]
+    L.pk_bank_generic_parts.restype = ctypes.c_uint32
+    L.pk_bank_generic_episode_bytes.argtypes = [vp]
+    L.pk_bank_generic_episode_bytes.restype = ctypes.c_uint64
 
 
 def check(rc: int, what: str):

@@ -54,6 +54,7 @@ hipError_t pk_launch_cell_keys(const uint8_t* mem, uint32_t sh, uint32_t shift, 
 hipError_t pk_launch_frame_keys(const PkCellArgs& a, hipStream_t s);
 hipError_t pk_launch_fstack(const PkStackArgs& a, hipStream_t s);
 hipError_t pk_launch_probe(const PkProbeArgs& a, hipStream_t s);
+hipError_t pk_launch_gep_move(const PkGepArgs& a, hipStream_t s);
 hipError_t pk_launch_cnt_update(const PkCountArgs& a, hipStream_t s);
 hipError_t pk_launch_cnt_add(const PkCountArgs& a, hipStream_t s);
 hipError_t pk_launch_cnt_pack(const PkCountArgs& a, hipStream_t s);
@@ -311,6 +312,14 @@ struct pk_handle {
     uint32_t* e_mask = nullptr;
     uint32_t* e_cutc = nullptr;
     uint8_t* b_ep_filled = nullptr;
+    // generic episode parts of the slots (pk_bank_enable_generic_episodes; pk_layout.h PkGepArgs), on a
+    // handle without the reward stack: gep_parts = the parts asked for | 0x80000000 once enabled, the
+    // raw registers, and the probe words and stack rows where asked for.  b_ep_filled is the flag array
+    // of these parts too, so the bank list's validation and the archive work unchanged
+    uint32_t gep_parts = 0;
+    uint32_t* g_regs = nullptr;
+    uint32_t* g_probe = nullptr;
+    uint8_t* g_stack = nullptr;
     // exploration archive (pk_archive_create; pk_layout.h PkArchArgs), arch_cells = 0 without one:
     // the persistent part, and the per-call words of an update in two blocks, one cleared to all
     // ones (empty keys, the min words) and one to zero (the max words, the counts)
@@ -388,7 +397,7 @@ void pk_destroy(pk_handle* h) {
                     h->b_mem, h->b_regs, h->b_lat, h->b_screen, h->b_filled, h->b_rejects, h->b_lists, h->b_src,
                     h->e_fields, h->e_seen, h->e_mask, h->e_cutc, h->b_ep_filled, h->a_fix, h->a_ones, h->a_zero,
                     h->x_fix, h->x_ones, h->x_zero, h->t_act, h->t_origin, h->t_flags, h->bt_act, h->bt_origin, h->bt_flags,
-                    h->c_fix, h->fs_stack, h->pr_prog, h->pr_state};
+                    h->c_fix, h->fs_stack, h->pr_prog, h->pr_state, h->g_regs, h->g_probe, h->g_stack};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     delete h;
@@ -649,6 +658,10 @@ static PkTrajArgs traj_args(pk_handle* h, uint32_t env0, uint32_t env1) {
     a.act = h->t_act; a.origin = h->t_origin; a.flags = h->t_flags;
     a.b_act = h->bt_act; a.b_origin = h->bt_origin; a.b_flags = h->bt_flags;
     a.e_fields = h->e_fields; a.b_ep_filled = h->b_ep_filled;
+    a.e_stride = PK_EP_WORDS; a.e_time = PK_EP_REGS + PK_R_TIME;
+    if (h->gep_parts) {   // a slot's length is the step counter among its raw registers
+        a.e_fields = h->g_regs; a.e_stride = PK_GEP_REGS; a.e_time = PK_R_TIME;
+    }
     a.cap = h->traj_cap; a.env0 = env0; a.env1 = env1;
     return a;
 }
@@ -706,11 +719,13 @@ static int traj_alloc(size_t rows, uint32_t cap, const std::vector<uint32_t>& fl
 static uint32_t traj_cap_of(uint32_t cap_log2) { return 3u << (cap_log2 - 2u); }
 
 // the trajectory parts of a seen set grown to 1 << need: new rows for the envs, every one flagged
-// PK_TRAJ_BROKEN (its actions stay behind), and for the slots where the bank has them
+// PK_TRAJ_BROKEN (its actions stay behind), and for the slots where the bank has them (their
+// episode parts are emptied by the caller; generic parts stay, so those rows are flagged too)
 static int traj_grow_alloc(pk_handle* h, uint32_t need, TrajBufs& envs, TrajBufs& slots) {
     if (!h->traj_cap) return 0;
     int rc = traj_alloc(h->npad, traj_cap_of(need), std::vector<uint32_t>(h->npad, PK_TRAJ_BROKEN), envs);
-    if (!rc && h->bt_act && (rc = traj_alloc(h->bank_n, traj_cap_of(need), std::vector<uint32_t>(h->bank_n, 0u), slots)))
+    if (!rc && h->bt_act && (rc = traj_alloc(h->bank_n, traj_cap_of(need),
+                                          std::vector<uint32_t>(h->bank_n, h->gep_parts ? PK_TRAJ_BROKEN : 0u), slots)))
         traj_free(envs);
     return rc;
 }
@@ -1482,6 +1497,63 @@ int pk_bank_enable_episodes(pk_handle* h) {
     return 0;
 }
 
+// ---- generic episode parts: checkpoints without the reward stack -------------------------------
+
+static uint32_t gep_mpad(const pk_handle* h, uint32_t parts) { return (parts & PK_GEP_PROBES) ? (h->pr_m + 3u) / 4u * 4u : 0u; }
+static uint32_t gep_row(const pk_handle* h, uint32_t parts) {
+    return (parts & PK_GEP_STACK) ? h->fs_depth * (PK_SCREEN / (h->fs_scale * h->fs_scale)) : 0u;
+}
+
+uint32_t pk_bank_generic_parts(const pk_handle* h) { return h ? h->gep_parts : 0; }
+
+uint64_t pk_bank_generic_episode_bytes(const pk_handle* h) {
+    if (!h || !h->gep_parts) return 0;
+    return (uint64_t)PK_GEP_REGS * 4u + (uint64_t)gep_mpad(h, h->gep_parts) * 4u + gep_row(h, h->gep_parts);
+}
+
+int pk_bank_enable_generic_episodes(pk_handle* h, uint32_t parts) {
+    if (!h) return fail(-EINVAL, "null handle");
+    if (h->flags & PK_F_REWARD)
+        return fail(-ENOTSUP, "generic episode parts are for handles without the reward stack (pk_bank_enable_episodes)");
+    if (!h->bank_n) return fail(-ENOENT, "the handle has no bank (pk_bank_create)");
+    if (parts & ~(PK_GEP_PROBES | PK_GEP_STACK)) return fail(-EINVAL, "unknown parts 0x%x", parts);
+    if ((parts & PK_GEP_PROBES) && !h->pr_m) return fail(-ENOENT, "PK_GEP_PROBES: the handle has no probe program (pk_probe_create)");
+    if ((parts & PK_GEP_STACK) && !h->fs_depth) return fail(-ENOENT, "PK_GEP_STACK: the handle has no frame stack (pk_fstack_create)");
+    if (h->b_ep_filled) return fail(-EEXIST, "the bank already carries episode parts");
+    static_assert(PK_GEP_REGS % 4u == 0u && PK_GEP_REGS >= PK_NREGS && PK_GEP_REGS <= 64u && PK_PROBE_MAX <= 64u &&
+                  PK_SCREEN % 256u == 0u, "generic episode part layout");
+    HIPCHK(hipSetDevice(h->device));
+    const size_t K = h->bank_n, rb = K * PK_GEP_REGS * 4, pb = K * gep_mpad(h, parts) * 4, sb = K * gep_row(h, parts);
+    uint32_t *gr = nullptr, *gp = nullptr;
+    uint8_t *gs = nullptr, *fl = nullptr;
+    // on a handle with trajectories the slots carry a trajectory part from the start
+    TrajBufs tb;
+    int rc;
+    if (h->traj_cap && (rc = traj_alloc(K, h->traj_cap, std::vector<uint32_t>(K, 0u), tb))) return rc;
+    hipError_t e = hipMalloc((void**)&gr, rb);
+    if (e == hipSuccess && pb) e = hipMalloc((void**)&gp, pb);
+    if (e == hipSuccess && sb) e = hipMalloc((void**)&gs, sb);
+    if (e == hipSuccess) e = hipMalloc((void**)&fl, K);
+    if (e == hipSuccess) e = hipMemset(gr, 0, rb);
+    if (e == hipSuccess && pb) e = hipMemset(gp, 0, pb);
+    if (e == hipSuccess && sb) e = hipMemset(gs, 0, sb);
+    if (e == hipSuccess) e = hipMemset(fl, 0, K);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        void* ptrs[] = {gr, gp, gs, fl};
+        for (void* p : ptrs)
+            if (p) (void)hipFree(p);
+        traj_free(tb);
+        (void)hipGetLastError();
+        return fail(-ENOMEM, "generic episode parts of %zu slots (%zu bytes each): %s", K, (rb + pb + sb) / K + 1,
+                    hipGetErrorString(e));
+    }
+    h->g_regs = gr; h->g_probe = gp; h->g_stack = gs; h->b_ep_filled = fl;
+    h->gep_parts = parts | 0x80000000u;
+    h->bt_act = tb.act; h->bt_origin = tb.origin; h->bt_flags = tb.flags;
+    return 0;
+}
+
 // pk_bank_save / pk_bank_load with ep set (the same lists, validation and launches), then the
 // episode mover over the same list, and for a resume the observation of the listed envs
 static int episode_move(pk_handle* h, uint32_t mode, const int32_t* slots, uint32_t env0, uint32_t count, void* stream) {
@@ -1497,6 +1569,26 @@ static int episode_move(pk_handle* h, uint32_t mode, const int32_t* slots, uint3
     HIPCHK(hipMemsetAsync(a.cnt, 0, 8, s));
     HIPCHK(pk_launch_bank_list(a, s));
     HIPCHK(pk_launch_bank_copy(a, s));
+    if (h->gep_parts) {
+        // no reward stack: the generic mover over the same list, then the trajectory part; there is
+        // no reward observation to rebuild
+        PkGepArgs g;
+        memset(&g, 0, sizeof g);
+        g.regs = h->regs; g.g_regs = h->g_regs;
+        if (h->gep_parts & PK_GEP_PROBES) { g.state = h->pr_state; g.g_probe = h->g_probe; g.m = h->pr_m; }
+        if (h->gep_parts & PK_GEP_STACK) { g.stack = h->fs_stack; g.g_stack = h->g_stack; }
+        g.mpad = gep_mpad(h, h->gep_parts); g.row16 = gep_row(h, h->gep_parts) / 16u;
+        g.cnt = a.cnt; g.ids = a.ids; g.src = a.src;
+        g.npad = h->npad; g.save = mode == PK_BANK_SAVE ? 1u : 0u; g.items = count;
+        HIPCHK(pk_launch_gep_move(g, s));
+        if (h->traj_cap) {
+            PkTrajArgs t = traj_args(h, env0, env0 + count);
+            t.cnt = a.cnt; t.ids = a.ids; t.src = a.src;
+            t.save = g.save; t.items = count;
+            HIPCHK(pk_launch_traj_move(t, s));
+        }
+        return 0;
+    }
     PkEpArgs p;
     memset(&p, 0, sizeof p);
     p.regs = h->regs; p.rs = h->rs; p.rsd = h->rsd; p.seen = h->seen; p.mask = h->mask; p.cutc = h->cutc;
@@ -1925,6 +2017,7 @@ static size_t xchg_zero_bytes(uint32_t cells, uint32_t ssize) { return 16 + ((si
 int pk_archive_exchange_enable(pk_handle* h) {
     if (!h) return fail(-EINVAL, "null handle");
     if (!h->arch_cells) return fail(-ENOENT, "the handle has no archive (pk_archive_create)");
+    if (h->gep_parts) return fail(-ENOTSUP, "the exchange payload has no format for generic episode parts");
     if (h->x_fix) return fail(-EEXIST, "the archive already has its exchange words");
     HIPCHK(hipSetDevice(h->device));
     const uint32_t K = h->arch_cells, R = PK_XCHG_MAX_RECORDS, S = pow2_at_least(2ull * R);

@@ -1210,6 +1210,56 @@ hipError_t pk_launch_probe(const PkProbeArgs& a, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Generic episode mover (pk_bank_checkpoint / pk_bank_resume on a handle without the reward stack;
+// pk_layout.h PkGepArgs): the generic episode part of the envs on the range's bank list <-> their
+// validated slots, shaped like pk_ep_move_kernel.  A stack row is linear on both sides, so a
+// workgroup takes one listed env and PK_GEP_CHUNK 16-byte pieces of its row, consecutive lanes
+// moving consecutive pieces; untouched envs are never scanned.  The workgroup of an env's first
+// chunk also moves the strided words, one lane per word: the lane registers (lanes 0..19) and the
+// probe state (lanes 64..64 + mpad), pad words written as 0 on a save and skipped on a load.
+// Without a stack part there is one chunk per env and only that tail runs.  No LDS, no atomics, no
+// barrier; rows are only read on the slot side of a resume, so many envs may name one slot.
+__global__ void __launch_bounds__(256) pk_gep_move_kernel(PkGepArgs A) {
+    const u32 np = A.npad, pieces = A.row16;
+    const u32 chunks = pieces ? (pieces + PK_GEP_CHUNK - 1u) / PK_GEP_CHUNK : 1u;
+    const u32 total = *A.cnt * chunks;
+    for (u32 w = blockIdx.x; w < total; w += gridDim.x) {
+        const u32 env = A.ids[w / chunks], c = w % chunks, s = (u32)A.src[env];
+        if (pieces) {
+            uint4* es = reinterpret_cast<uint4*>(A.stack + (size_t)env * pieces * 16u);
+            uint4* bs = reinterpret_cast<uint4*>(A.g_stack + (size_t)s * pieces * 16u);
+            const u32 q1 = (c + 1u) * PK_GEP_CHUNK < pieces ? (c + 1u) * PK_GEP_CHUNK : pieces;
+            for (u32 q = c * PK_GEP_CHUNK + threadIdx.x; q < q1; q += blockDim.x) {
+                if (A.save) bs[q] = es[q];
+                else es[q] = bs[q];
+            }
+        }
+        if (c != 0u) continue;
+        const u32 t = threadIdx.x;
+        if (t < PK_GEP_REGS) {
+            u32* b = A.g_regs + (size_t)s * PK_GEP_REGS + t;
+            u32* p = t < PK_NREGS ? A.regs + (size_t)t * np + env : nullptr;
+            if (A.save) *b = p ? *p : 0u;
+            else if (p) *p = *b;
+        } else if (t >= 64u && t < 64u + A.mpad) {
+            const u32 j = t - 64u;
+            u32* b = A.g_probe + (size_t)s * A.mpad + j;
+            u32* p = j < A.m ? A.state + (size_t)j * np + env : nullptr;
+            if (A.save) *b = p ? *p : 0u;
+            else if (p) *p = *b;
+        }
+    }
+}
+
+hipError_t pk_launch_gep_move(const PkGepArgs& a, hipStream_t s) {
+    const u32 chunks = a.row16 ? (a.row16 + PK_GEP_CHUNK - 1u) / PK_GEP_CHUNK : 1u;
+    const uint64_t items = (uint64_t)a.items * chunks;
+    const u32 grid = items < 65536u ? (u32)(items ? items : 1u) : 65536u;
+    hipLaunchKernelGGL(pk_gep_move_kernel, dim3(grid), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
 // Archive exchange (pk_archive_pack / pk_archive_merge): cells as records and whole-slot payloads.
 
 // pk_archive_pack, one workgroup: the records of cells [cell0, cell0 + count) and, by a scan in cell

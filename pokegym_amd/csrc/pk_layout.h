@@ -405,3 +405,31 @@ struct PkProbeArgs {
     uint32_t ilv_sh;
     uint32_t rebase_only, set;
 };
+
+// Generic episode part of a bank slot (pk_bank_enable_generic_episodes): what an episode consists of
+// on a handle without the reward stack, one array per part, every part of a slot 16-byte aligned.
+//   g_regs   u32[n_slots][PK_GEP_REGS]  all PK_NREGS lane registers raw (the machine part stores
+//            PK_R_TIME / PK_R_ICOUNT / PK_R_RFLAGS as 0, PK_R_MISC as "nothing held" and drops the
+//            register bits a v9 state has no room for), padded to whole 16-byte pieces with 0
+//   g_probe  u32[n_slots][mpad]         PK_GEP_PROBES: word j = state[j * npad + env], m padded to 4
+//   g_stack  u8[n_slots][row16 * 16]    PK_GEP_STACK: the env's row of the frame stack, linear on
+//            both sides in both layouts (H * W is a multiple of 16)
+#define PK_GEP_REGS ((PK_NREGS + 3u) / 4u * 4u)
+#define PK_GEP_CHUNK 1024u       // 16-byte pieces of a stack row one workgroup pass moves
+
+struct PkGepArgs {
+    uint32_t* regs;              // K1 lane registers [PK_NREGS][npad]
+    uint32_t* state;             // probe state [m][npad]; null without PK_GEP_PROBES
+    uint8_t* stack;              // [n][row16 * 16]; null without PK_GEP_STACK
+    uint32_t* g_regs;            // [n_slots][PK_GEP_REGS]
+    uint32_t* g_probe;           // [n_slots][mpad]
+    uint8_t* g_stack;            // [n_slots][row16 * 16]
+    const uint32_t* cnt;         // the range's bank list (pk_bank_list_kernel): count ...
+    const uint32_t* ids;         // ... env ids ...
+    const int32_t* src;          // ... and the validated slot of every env
+    uint32_t npad;
+    uint32_t m, mpad;            // probes carried (0 without the part) and their padded count, <= 64
+    uint32_t row16;              // 16-byte pieces of a stack row, 0 without the part
+    uint32_t save;               // 1 = checkpoint (env -> slot), 0 = resume (slot -> env)
+    uint32_t items;              // upper bound of listed envs (the range's size): sizes the grid
+};

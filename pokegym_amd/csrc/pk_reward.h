@@ -125,7 +125,8 @@ struct PkEpArgs {
 // cap = 3 << (cap_log2 - 2), a multiple of 16 that is >= max_episode_steps.  Rows are env-major,
 // u8[npad][cap], so a row is linear memory and starts 16-byte aligned.  When the bank carries
 // episode parts every slot has the same three parts; a slot's length is the step counter of its
-// episode record (e_fields, PK_EP_REGS + PK_R_TIME).  The flags are kept a word per env and slot:
+// episode record (e_fields, PK_EP_REGS + PK_R_TIME; on a handle with generic episode parts the
+// raw registers of g_regs, PK_R_TIME).  The flags are kept a word per env and slot:
 // the mover makes no byte access.
 #ifndef PK_TRAJ_BROKEN
 #define PK_TRAJ_BROKEN 1u     // == include/pokegym_amd.h
@@ -141,7 +142,9 @@ struct PkTrajArgs {
     uint8_t* b_act;           // [n_slots][cap], null while the bank carries no episodes
     int32_t* b_origin;        // [n_slots]
     uint32_t* b_flags;        // [n_slots]
-    const uint32_t* e_fields; // [n_slots][PK_EP_WORDS] the slots' episode records (their lengths)
+    const uint32_t* e_fields; // the slots' episode records (their lengths): [n_slots][e_stride] words, the step
+    uint32_t e_stride, e_time;// counter at word e_time — PK_EP_WORDS and PK_EP_REGS + PK_R_TIME, or the
+                              // generic part's PK_GEP_REGS and PK_R_TIME (pk_layout.h PkGepArgs)
     const uint8_t* b_ep_filled;
     const uint8_t* actions;   // record: the step's actions [n]
     const uint8_t* mask;      // reset: the envs that were reset (null = all)

@@ -921,7 +921,7 @@ __global__ void __launch_bounds__(256) pk_traj_get_kernel(PkTrajArgs A) {
             row = reinterpret_cast<const uint4*>(A.act + (size_t)i * A.cap);
         } else if (A.b_ep_filled && A.b_ep_filled[i]) {
             origin = A.b_origin[i];
-            len = A.e_fields[(size_t)i * PK_EP_WORDS + PK_EP_REGS + PK_R_TIME];
+            len = A.e_fields[(size_t)i * A.e_stride + A.e_time];
             flags = A.b_flags[i];
             row = reinterpret_cast<const uint4*>(A.b_act + (size_t)i * A.cap);
         }

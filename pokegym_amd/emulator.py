@@ -204,6 +204,26 @@ class BatchedEmulator:
     def bank_has_episodes(self) -> bool:
         return bool(self._L.pk_bank_has_episodes(self._h))
 
+    def bank_enable_generic_episodes(self, probes: bool = True, stack: bool = True):
+        """Let the bank's slots of an emulator with reward=False carry generic episode parts: every lane
+        register raw, with probes=True the probe state words, with stack=True the frame stack rows
+        (pk_bank_enable_generic_episodes; once, synchronous; needs a bank, and probes_create /
+        stack_create before it for the parts asked for).  bank_checkpoint, bank_resume and the archive
+        then work as on a reward emulator."""
+        parts = (_native.PK_GEP_PROBES if probes else 0) | (_native.PK_GEP_STACK if stack else 0)
+        check(self._L.pk_bank_enable_generic_episodes(self._h, parts), "pk_bank_enable_generic_episodes")
+
+    @property
+    def generic_parts(self) -> int | None:
+        """The PK_GEP_* parts the slots carry, None without generic episode parts."""
+        v = int(self._L.pk_bank_generic_parts(self._h))
+        return (v & 0x7FFFFFFF) if v else None
+
+    @property
+    def generic_episode_bytes(self) -> int:
+        """Bytes per slot of the generic episode part, 0 without."""
+        return int(self._L.pk_bank_generic_episode_bytes(self._h))
+
     def bank_checkpoint(self, slot_of_env: torch.Tensor, env0: int = 0, count: int | None = None):
         """bank_save plus the episode part of every saved env: step counter, reward bookkeeping, seen
         set, visited mask (pk_bank_checkpoint, on the current stream)."""

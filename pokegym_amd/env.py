@@ -261,7 +261,7 @@ class VecEnv:
                  device: int | None = None, max_episode_steps: int = 20480, reward_scale: float = 4.0,
                  reload_on_reset: bool = False, env_offset: int = 0, log_interval: int = 128, emulator=None,
                  heatmap: bool = False, reward: bool = True, power_on: bool = False, batch_size: int | None = None,
-                 state_pool=None, pool_seed: int = 0, bank_slots: int = 0, bank_episodes: bool = False,
+                 state_pool=None, pool_seed: int = 0, bank_slots: int = 0, bank_episodes: bool | str = False,
                  fork_slots: int = 0, archive_cells: int = 0, archive_seed: int = 0, archive_shift: int = 0,
                  record_trajectories: bool = False, archive_exchange: bool = False, archive_key: str = "ram",
                  archive_frame=(16, 16, 8), novelty_log2: int = 0, novelty_beta: float = 1.0, novelty_key: str = "frame",
@@ -286,6 +286,17 @@ class VecEnv:
         this class's per-env episode return / length and start slot travel with it.  fork_slots
         reserves that many scratch slots after the pool's and the user's for fork(): the number of
         distinct source envs one fork() call can copy.
+
+        bank_episodes="generic" (needs reward=False) is the same on any cartridge: the slots carry generic
+        episode parts (pk_bank_enable_generic_episodes) — the raw lane registers with the step counter,
+        and whatever of probes= and frame_stack= the env has, the probe state words and the stack rows —
+        so checkpoint_to_bank, resume_from_bank, fork, fork_slots, archive_cells (archive_key="frame";
+        "ram" and "frame+ram" stay legal but read Pokémon Red's addresses) and record_trajectories work
+        as for reward envs, with the frame key and the probe return.  A resumed env keeps the
+        checkpoint's frames and probe state: resume_from_bank, fork and archive_explore neither refill
+        nor rebase, a resumed "newmax" keeps its maximum, and with probe_features the feature rows
+        travel per slot like the episode return, so probe_values shows the checkpoint's values.
+        archive_exchange=True raises: the exchange payload has no format for generic parts.
 
         archive_cells=K (needs bank_episodes=True) adds K more slots after those and an exploration
         archive over them (pk_archive_*): archive_update() keeps the best episode per cell key,
@@ -344,8 +355,8 @@ class VecEnv:
         auto-reset rebases the envs that were reset, so their next step is measured from the reset
         state.  reset() rebases every env, and load_from_bank, resume_from_bank, fork, archive_explore
         and load_state rebase the envs whose machine they replaced, at the sites and with the masks of
-        the frame stack's refill: the probe state does not travel through the bank, a resumed
-        "newmax" starts again from the current value.  probe_features=True also keeps the probe values:
+        the frame stack's refill: without bank_episodes="generic" the probe state does not travel through
+        the bank, a resumed "newmax" starts again from the current value.  probe_features=True also keeps the probe values:
         probe_values is int32 (num_envs, m), the values every env's last step ended on (probe_space).
         With None nothing is allocated or launched."""
         self.batch_size = batch_size or num_envs
@@ -436,7 +447,16 @@ class VecEnv:
         self._cap_lg = _seen_cap_log2(getattr(emulator, "max_episode_steps", 20480))
         self._fork0 = 0             # first scratch slot of fork()
         self._ck_return = self._ck_length = self._ck_slots = self._ck_valid = None
-        if bank_episodes and not getattr(emulator, "reward", False):
+        self._ck_feat = None        # generic episodes with probe_features: the feature row per slot
+        self._generic = isinstance(bank_episodes, str)
+        if self._generic:
+            if bank_episodes != "generic":
+                raise ValueError(f'bank_episodes must be True, False or "generic", not {bank_episodes!r}')
+            if getattr(emulator, "reward", False):
+                raise ValueError('bank_episodes="generic" is for emulators without the reward stack (reward=False)')
+            if archive_exchange:
+                raise ValueError('archive_exchange needs bank_episodes=True: generic episode parts have no exchange payload')
+        elif bank_episodes and not getattr(emulator, "reward", False):
             raise ValueError("bank_episodes=True needs the reward stack (reward=True)")
         if self.fork_slots and not bank_episodes:
             raise ValueError("fork_slots needs bank_episodes=True")
@@ -482,7 +502,10 @@ class VecEnv:
             if bank_episodes:
                 # what this class keeps per env of an episode, per slot: taken at a checkpoint,
                 # restored at a resume (device tensors, no host copy)
-                self.emu.bank_enable_episodes()
+                if self._generic:   # the parts of what this env has; both were created above
+                    self.emu.bank_enable_generic_episodes(probes=self.probes is not None, stack=bool(self.frame_stack))
+                else:
+                    self.emu.bank_enable_episodes()
                 # (one entry past the last slot takes the writes of out-of-range slots, which the
                 # device rejects; _ck_valid mirrors the device's "holds an episode" flag)
                 k = self._arch0 + self.archive_cells + 1
@@ -490,6 +513,8 @@ class VecEnv:
                 self._ck_length = torch.zeros(k, dtype=torch.float64, device=self.device)
                 self._ck_slots = torch.full((k,), -1, dtype=torch.int32, device=self.device)
                 self._ck_valid = torch.zeros(k, dtype=torch.bool, device=self.device)
+                if self._generic and self._probe_feat is not None:
+                    self._ck_feat = torch.zeros((k, len(self.probes)), dtype=torch.int32, device=self.device)
                 if self.archive_cells:
                     self.emu.archive_create(self._arch0, self.archive_cells, archive_seed)
                     self._arch_out = torch.full((n_phys,), -1, dtype=torch.int32, device=self.device)
@@ -590,8 +615,11 @@ class VecEnv:
         self._ck_length[slots] = self.stats.ep_length[envs]
         self._ck_valid[slots] = True
         self._ck_valid[last] = False
+        phys = (envs // self.batch_size) * self.slot + envs % self.batch_size
+        if self._ck_feat is not None:
+            self._ck_feat[slots] = self._probe_feat[phys]
         if self._slots is not None:
-            self._ck_slots[slots] = self._slots[(envs // self.batch_size) * self.slot + envs % self.batch_size]
+            self._ck_slots[slots] = self._slots[phys]
 
     def resume_from_bank(self, envs, slots):
         """Env envs[i] continues the episode checkpointed in slot slots[i] (pk_bank_resume): fed the
@@ -611,7 +639,10 @@ class VecEnv:
         phys = (envs // self.batch_size) * self.slot + envs % self.batch_size
         if self._slots is not None:
             self._slots[phys] = torch.where(ok, self._ck_slots[slots], self._slots[phys])
-        if self.frame_stack or self.probes is not None:   # the resumed envs start a history of their own
+        if self._generic:           # stack rows and probe words came with the slot: no refill, no rebase
+            if self._ck_feat is not None:   # (an evaluation would pay reward) the checkpoint's feature rows
+                self._probe_feat[phys] = torch.where(ok[:, None], self._ck_feat[slots], self._probe_feat[phys])
+        elif self.frame_stack or self.probes is not None:   # the resumed envs start a history of their own
             m = torch.zeros(self.emu.n, dtype=torch.uint8, device=self.device)
             m[phys] = ok.to(torch.uint8)
             self._machines_replaced(m)
@@ -698,6 +729,8 @@ class VecEnv:
         self._ck_length[slots] = self.stats.ep_length
         self._ck_valid[slots] = True
         self._ck_valid[last] = False
+        if self._ck_feat is not None:
+            self._ck_feat[slots] = self._logical(self._probe_feat)
         if self._slots is not None:
             self._ck_slots[slots] = self._logical(self._slots)
         return won.to(torch.int32)
@@ -711,7 +744,8 @@ class VecEnv:
         self._join_streams()
         mask = self._physical(torch.as_tensor(mask, device=self.device) != 0, 0, torch.uint8)
         self.emu.archive_explore(mask, out=self._arch_out)
-        if self.frame_stack or self.probes is not None:   # the envs that resumed: the device's own answer, rejects excluded
+        # the envs that resumed: the device's own answer, rejects excluded (generic parts carry both)
+        if (self.frame_stack or self.probes is not None) and not self._generic:
             self._machines_replaced((self._arch_out >= 0).to(torch.uint8))
         drawn = self._logical(self._arch_out).long()
         last = self._ck_return.numel() - 1
@@ -719,6 +753,12 @@ class VecEnv:
         ok = (drawn >= 0) & self._ck_valid[slots]
         self.stats.ep_return.copy_(torch.where(ok, self._ck_return[slots], self.stats.ep_return))
         self.stats.ep_length.copy_(torch.where(ok, self._ck_length[slots], self.stats.ep_length))
+        if self._ck_feat is not None:
+            feat = torch.where(ok[:, None], self._ck_feat[slots], self._logical(self._probe_feat))
+            if self._padded:
+                self._probe_feat[self._phys] = feat
+            else:
+                self._probe_feat.copy_(feat)
         if self._slots is not None:
             cur = self._logical(self._slots)
             new = torch.where(ok, self._ck_slots[slots], cur)
@@ -885,7 +925,7 @@ class VecEnv:
             grows = _seen_cap_log2(mes) > self._cap_lg      # the seen set never shrinks
             self._cap_lg = max(self._cap_lg, _seen_cap_log2(mes))
             self.emu.set_episode_params(mes, rsc)
-            if grows and self._ck_return is not None:   # the device emptied every slot's episode part
+            if grows and self._ck_return is not None and not self._generic:   # the device emptied every slot's episode part
                 self._ck_valid.zero_()
         if self._slots is None:
             obs = self._logical(self.emu.reset())
