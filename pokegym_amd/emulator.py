@@ -47,10 +47,7 @@ class BatchedEmulator:
                  frame_skip: int = 24, release_frame: int = 8, render: bool = True,
                  max_episode_steps: int = 20480, reward: bool = False, reload_on_reset: bool = False,
                  reward_scale: float = 4.0, heatmap: bool = False):
-        self._L = _native.load()
-        if not torch.cuda.is_available():
-            raise _native.PkError("no ROCm GPU visible: the HIP path has no CPU fallback")
-        self.device = torch.device("cuda", device)
+        self._L, self.device, on_device = self._backend(device)
         self.n = int(n_envs)
         self._rom, rom_p = _u8p(rom)
         cfg = _native.PkConfig()
@@ -70,14 +67,14 @@ class BatchedEmulator:
         cfg.max_episode_steps = max_episode_steps
         cfg.reward_scale = reward_scale
         h = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
+        with on_device:
             check(self._L.pk_create(ctypes.byref(cfg), ctypes.byref(h)), "pk_create")
         self._h = h
         self.render = render
         self.reward = reward
         self.max_episode_steps, self.reward_scale = int(max_episode_steps), float(reward_scale)
-        ptr = self._L.pk_screen_ptr(self._h)
-        self.screen = torch.as_tensor(_CudaArray(ptr, (self.n, ROWS, COLS), "|u1"), device=self.device)
+        L, n = self._L, self.n
+        self.screen = self._view(L.pk_screen_ptr(h), (n, ROWS, COLS), "|u1")
         self.obs = None
         self.errors = None
         self.heatmap = None     # int32 (n, 444, 436) with heatmap=True
@@ -85,25 +82,35 @@ class BatchedEmulator:
         self.info = None        # f64 (PK_INFO_NFIELDS, n) view, field-major (pokegym_amd/info.py FIELDS)
         self.info_flag = None   # u8 (n,): 1 where the last step built the reference's info dict
         if reward:
-            self.obs = torch.as_tensor(_CudaArray(self._L.pk_obs_ptr(self._h), (self.n,) + OBS_SHAPE, "|u1"),
-                                       device=self.device)
-            self.errors = torch.as_tensor(_CudaArray(self._L.pk_error_ptr(self._h), (self.n,), "<i4"),
-                                          device=self.device)
-            stride = int(self._L.pk_info_stride(self._h))
-            full = torch.as_tensor(_CudaArray(self._L.pk_info_ptr(self._h), (NFIELDS, stride), "<f8"),
-                                   device=self.device)
-            self.info = full[:, :self.n]
-            bits = torch.as_tensor(_CudaArray(self._L.pk_info_bits_ptr(self._h), (5, stride), "<i4"), device=self.device)
-            self.info_bits = bits[:, :self.n]   # event-monitor bits (int32 words; pokegym_amd/info.py event_dicts)
-            self.info_flag = torch.as_tensor(_CudaArray(self._L.pk_info_flag_ptr(self._h), (self.n,), "|u1"),
-                                             device=self.device)
-            hp = self._L.pk_heatmap_ptr(self._h)
+            self.obs = self._view(L.pk_obs_ptr(h), (n,) + OBS_SHAPE, "|u1")
+            self.errors = self._view(L.pk_error_ptr(h), (n,), "<i4")
+            stride = int(L.pk_info_stride(h))
+            self.info = self._view(L.pk_info_ptr(h), (NFIELDS, stride), "<f8")[:, :n]
+            # event-monitor bits (int32 words; pokegym_amd/info.py event_dicts)
+            self.info_bits = self._view(L.pk_info_bits_ptr(h), (5, stride), "<i4")[:, :n]
+            self.info_flag = self._view(L.pk_info_flag_ptr(h), (n,), "|u1")
+            hp = L.pk_heatmap_ptr(h)
             if hp:   # int32 (n, 444, 436) counts_map of every env (environment.py:448, :648-679)
-                self.heatmap = torch.as_tensor(_CudaArray(hp, (self.n,) + _native.HEAT_SHAPE, "<i4"), device=self.device)
+                self.heatmap = self._view(hp, (n,) + _native.HEAT_SHAPE, "<i4")
         self.rewards = torch.zeros(self.n, dtype=torch.float64, device=self.device)
         self.terminals = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
         self.truncations = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
         self.actions = torch.full((self.n,), 8, dtype=torch.uint8, device=self.device)  # sub-batch staging
+
+    def _backend(self, device: int):
+        """What depends on where the handle's buffers live: the loaded library, the torch device, and the
+        context pk_create runs in.  The product has one backend: a ROCm GPU."""
+        L = _native.load()
+        if not torch.cuda.is_available():
+            raise _native.PkError("no ROCm GPU visible: the HIP path has no CPU fallback")
+        dev = torch.device("cuda", device)
+        return L, dev, torch.cuda.device(dev)
+
+    def _view(self, ptr: int, shape, typestr: str) -> torch.Tensor:
+        """A tensor over a handle-owned buffer on the handle's device, without a copy."""
+        if self.device.type == "cpu":
+            return torch.from_numpy(np.asarray(_HostArray(ptr, shape, typestr)))
+        return torch.as_tensor(_CudaArray(ptr, shape, typestr), device=self.device)
 
     # -- stream helpers -----------------------------------------------------------------
     def _stream(self):
@@ -504,12 +511,6 @@ class BatchedEmulator:
         check(self._L.pk_counts_clear(self._h, self._stream()), "pk_counts_clear")
 
     # -- frame stack (stream-ordered except create) ----------------------------------------
-    def _view(self, ptr: int, shape, typestr: str) -> torch.Tensor:
-        """A tensor over a handle-owned buffer on the handle's device, without a copy."""
-        if self.device.type == "cpu":
-            return torch.from_numpy(np.asarray(_HostArray(ptr, shape, typestr)))
-        return torch.as_tensor(_CudaArray(ptr, shape, typestr), device=self.device)
-
     def stack_create(self, scale: int = 2, depth: int = 4, layout: str = "chw", mode: str = "mean"):
         """Give the handle a frame stack: per env `depth` frames downscaled by `scale` (1, 2, 4), newest
         first, uint8 (n, depth, 144 / scale, 160 / scale) for layout "chw" or (n, 144 / scale,
@@ -785,7 +786,8 @@ class BatchedEmulator:
 
     def close(self):
         if getattr(self, "_h", None):
-            torch.cuda.synchronize(self.device)
+            if self.device.type == "cuda":
+                torch.cuda.synchronize(self.device)
             self.screen = None
             self.obs = None
             self.errors = None

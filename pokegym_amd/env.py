@@ -77,6 +77,62 @@ def _seen_cap_log2(max_episode_steps: int) -> int:
     return lg
 
 
+class SlotLedger:
+    """What VecEnv keeps of an episode per bank slot: one column per carried value, device tensors.
+
+    The columns' names are those of what an env carries (VecEnv._carried): "ret" and "length" (float64),
+    "start" (int32, the pool slot the episode started from; -1 without a pool) and, only for generic
+    episodes with probe_features, "feat" (int32 rows of `features` values).  `valid` mirrors the device's
+    "holds an episode" flag.  One row past the last slot is a sink: it takes the writes of the slots
+    the device rejects (negative or out of range) and is never valid."""
+
+    WIRE = ("ret", "length", "valid", "start")      # column order of rows(): a wire format between ranks
+
+    def __init__(self, n_slots: int, device, features: int = 0):
+        self.sink = n_slots
+        self.cols = {"ret": torch.zeros(n_slots + 1, dtype=torch.float64, device=device),
+                     "length": torch.zeros(n_slots + 1, dtype=torch.float64, device=device),
+                     "start": torch.full((n_slots + 1,), -1, dtype=torch.int32, device=device)}
+        if features:
+            self.cols["feat"] = torch.zeros((n_slots + 1, features), dtype=torch.int32, device=device)
+        self.valid = torch.zeros(n_slots + 1, dtype=torch.bool, device=device)
+
+    def _rows(self, slots: torch.Tensor) -> torch.Tensor:
+        slots = slots.long()
+        return torch.where((slots >= 0) & (slots < self.sink), slots, self.sink)
+
+    def store(self, slots: torch.Tensor, values: dict, valid=True):
+        """values[name][i] (and valid, or valid[i]) into slot slots[i]; a rejected slot stores nothing."""
+        rows = self._rows(slots)
+        for name, v in values.items():
+            self.cols[name][rows] = v.to(self.cols[name].dtype)
+        self.valid[rows] = valid
+        self.valid[self.sink] = False
+
+    def fetch(self, slots: torch.Tensor):
+        """(ok, values): values[name][i] is slot slots[i]'s, ok[i] whether that slot holds an episode."""
+        rows = self._rows(slots)
+        return self.valid[rows], {name: col[rows] for name, col in self.cols.items()}
+
+    def invalidate(self, slots: torch.Tensor | None = None):
+        """The slots (None: every slot) hold no episode any more."""
+        if slots is None:
+            self.valid.zero_()
+        else:
+            self.valid[self._rows(slots)] = False
+
+    def rows(self, slot0: int, count: int) -> torch.Tensor:
+        """Slots [slot0, slot0 + count) as float64 (count, 4) rows in WIRE order, as the exchange sends them."""
+        sl = slice(slot0, slot0 + count)
+        return torch.stack([(self.valid if name == "valid" else self.cols[name])[sl].to(torch.float64)
+                            for name in self.WIRE], dim=1)
+
+    def place(self, slots: torch.Tensor, rows: torch.Tensor):
+        """rows() rows back into slots[i]; the row of a rejected slot goes nowhere."""
+        cols = dict(zip(self.WIRE, rows.unbind(1)))
+        self.store(slots, {name: v for name, v in cols.items() if name != "valid"}, cols["valid"] != 0)
+
+
 class Base:
     """pokegym.environment.Base (environment.py:89-434): the emulator surface without the reward
     stack — step(action) runs the action and returns (render(), 0, False, False, {}) (:404-406),
@@ -360,9 +416,9 @@ class VecEnv:
         probe_values is int32 (num_envs, m), the values every env's last step ended on (probe_space).
         With None nothing is allocated or launched."""
         self.batch_size = batch_size or num_envs
-        if num_envs % self.batch_size:
+        self.num_batches, rest = divmod(num_envs, self.batch_size)
+        if rest:
             raise ValueError("batch_size must divide num_envs")
-        self.num_batches = num_envs // self.batch_size
         # slot of a sub-batch in the emulator: batch_size rounded up to a 64-env group
         self.slot = (self.batch_size if self.num_batches == 1 or self.batch_size % 64 == 0
                      else -(-self.batch_size // 64) * 64)
@@ -384,8 +440,7 @@ class VecEnv:
         self.num_envs = self.num_agents = num_envs
         # emulator index of every env (only differs from the env index when slots are padded)
         self._padded = n_phys != num_envs
-        self._phys = (torch.cat([torch.arange(b * self.slot, b * self.slot + self.batch_size)
-                                 for b in range(self.num_batches)]).to(self.device) if self._padded else None)
+        self._phys = self.phys(torch.arange(num_envs)).to(self.device) if self._padded else None
         self.single_observation_space = (spaces.observation_space() if getattr(emulator, "reward", True)
                                          else spaces.screen_space())
         self.frame_stack = 0 if frame_stack is None else frame_stack
@@ -446,8 +501,7 @@ class VecEnv:
         self.fork_slots = int(fork_slots)
         self._cap_lg = _seen_cap_log2(getattr(emulator, "max_episode_steps", 20480))
         self._fork0 = 0             # first scratch slot of fork()
-        self._ck_return = self._ck_length = self._ck_slots = self._ck_valid = None
-        self._ck_feat = None        # generic episodes with probe_features: the feature row per slot
+        self._ledger = None         # SlotLedger with bank_episodes
         self._generic = isinstance(bank_episodes, str)
         if self._generic:
             if bank_episodes != "generic":
@@ -506,15 +560,9 @@ class VecEnv:
                     self.emu.bank_enable_generic_episodes(probes=self.probes is not None, stack=bool(self.frame_stack))
                 else:
                     self.emu.bank_enable_episodes()
-                # (one entry past the last slot takes the writes of out-of-range slots, which the
-                # device rejects; _ck_valid mirrors the device's "holds an episode" flag)
-                k = self._arch0 + self.archive_cells + 1
-                self._ck_return = torch.zeros(k, dtype=torch.float64, device=self.device)
-                self._ck_length = torch.zeros(k, dtype=torch.float64, device=self.device)
-                self._ck_slots = torch.full((k,), -1, dtype=torch.int32, device=self.device)
-                self._ck_valid = torch.zeros(k, dtype=torch.bool, device=self.device)
-                if self._generic and self._probe_feat is not None:
-                    self._ck_feat = torch.zeros((k, len(self.probes)), dtype=torch.int32, device=self.device)
+                # (generic episodes with probe_features: the feature row travels per slot too)
+                self._ledger = SlotLedger(self._arch0 + self.archive_cells, self.device,
+                                          len(self.probes) if self._generic and self._probe_feat is not None else 0)
                 if self.archive_cells:
                     self.emu.archive_create(self._arch0, self.archive_cells, archive_seed)
                     self._arch_out = torch.full((n_phys,), -1, dtype=torch.int32, device=self.device)
@@ -549,9 +597,8 @@ class VecEnv:
         slots = torch.as_tensor(slots, device=self.device).reshape(-1).to(torch.int32)
         if envs.numel() != slots.numel():
             raise ValueError("envs and slots must have the same length")
-        phys = (envs // self.batch_size) * self.slot + envs % self.batch_size
         out = torch.full((self.emu.n,), -1, dtype=torch.int32, device=self.device)
-        out[phys] = slots
+        out[self.phys(envs)] = slots
         return out
 
     def save_to_bank(self, envs, slots, check: bool = True):
@@ -566,10 +613,8 @@ class VecEnv:
                 raise ValueError("save_to_bank: a slot is named twice")
         self._join_streams()
         self.emu.bank_save(self._bank_map(envs, slots))
-        if self._ck_return is not None:     # a plain save leaves the slot without an episode
-            last = self._ck_return.numel() - 1
-            s = torch.as_tensor(slots, device=self.device).reshape(-1).long()
-            self._ck_valid[torch.where((s >= 0) & (s < last), s, last)] = False
+        if self._ledger is not None:        # a plain save leaves the slot without an episode
+            self._ledger.invalidate(torch.as_tensor(slots, device=self.device).reshape(-1))
 
     def load_from_bank(self, envs, slots):
         """Load bank slot slots[i] into env envs[i] (pk_bank_load: machine state only, the episode's
@@ -590,9 +635,36 @@ class VecEnv:
         if self.probes is not None:
             self.emu.probes_eval(mask, rebase_only=True, features=self._probe_feat)
 
+    def _carried(self) -> dict:
+        """Everything of an episode that this class keeps per env and that travels through a bank slot:
+        SlotLedger column -> (tensor, whether it is in emulator order); the others are in env order."""
+        c = {"ret": (self.stats.ep_return, False), "length": (self.stats.ep_length, False)}
+        if self._slots is not None:
+            c["start"] = (self._slots, True)
+        if "feat" in self._ledger.cols:
+            c["feat"] = (self._probe_feat, True)
+        return c
+
+    def _gather(self, envs: torch.Tensor | None = None) -> dict:
+        """What the envs (None: every env, in env order) carry, for SlotLedger.store."""
+        if envs is None:
+            return {name: self._logical(t) if emu_order else t for name, (t, emu_order) in self._carried().items()}
+        return {name: t[self.phys(envs) if emu_order else envs] for name, (t, emu_order) in self._carried().items()}
+
+    def _scatter(self, values: dict, ok: torch.Tensor, envs: torch.Tensor | None = None):
+        """The reverse: envs[i] (None: env i) takes values[name][i] where ok[i]; the others keep theirs."""
+        for name, (t, emu_order) in self._carried().items():
+            take = ok if t.dim() == 1 else ok[:, None]
+            if envs is not None:
+                idx = self.phys(envs) if emu_order else envs
+                t[idx] = torch.where(take, values[name], t[idx])
+            elif emu_order:
+                self._set_physical(t, torch.where(take, values[name], self._logical(t)))
+            else:
+                t.copy_(torch.where(take, values[name], t))
+
     def _episode_args(self, envs, slots):
-        if self._ck_return is None:
-            raise RuntimeError("VecEnv(bank_episodes=True) keeps episode checkpoints")
+        self._require("episodes")
         envs = torch.as_tensor(envs, device=self.device).reshape(-1).long()
         slots = torch.as_tensor(slots, device=self.device).reshape(-1).long()
         if envs.numel() != slots.numel():
@@ -609,17 +681,7 @@ class VecEnv:
             raise ValueError("checkpoint_to_bank: a slot is named twice")
         self._join_streams()
         self.emu.bank_checkpoint(self._bank_map(envs, slots))
-        last = self._ck_return.numel() - 1
-        slots = torch.where((slots >= 0) & (slots < last), slots, last)
-        self._ck_return[slots] = self.stats.ep_return[envs]
-        self._ck_length[slots] = self.stats.ep_length[envs]
-        self._ck_valid[slots] = True
-        self._ck_valid[last] = False
-        phys = (envs // self.batch_size) * self.slot + envs % self.batch_size
-        if self._ck_feat is not None:
-            self._ck_feat[slots] = self._probe_feat[phys]
-        if self._slots is not None:
-            self._ck_slots[slots] = self._slots[phys]
+        self._ledger.store(slots, self._gather(envs))
 
     def resume_from_bank(self, envs, slots):
         """Env envs[i] continues the episode checkpointed in slot slots[i] (pk_bank_resume): fed the
@@ -631,20 +693,14 @@ class VecEnv:
         envs, slots = self._episode_args(envs, slots)
         self._join_streams()
         self.emu.bank_resume(self._bank_map(envs, slots))
-        last = self._ck_return.numel() - 1
-        slots = torch.where((slots >= 0) & (slots < last), slots, last)
-        ok = self._ck_valid[slots]           # the envs the device does not reject
-        self.stats.ep_return[envs] = torch.where(ok, self._ck_return[slots], self.stats.ep_return[envs])
-        self.stats.ep_length[envs] = torch.where(ok, self._ck_length[slots], self.stats.ep_length[envs])
-        phys = (envs // self.batch_size) * self.slot + envs % self.batch_size
-        if self._slots is not None:
-            self._slots[phys] = torch.where(ok, self._ck_slots[slots], self._slots[phys])
-        if self._generic:           # stack rows and probe words came with the slot: no refill, no rebase
-            if self._ck_feat is not None:   # (an evaluation would pay reward) the checkpoint's feature rows
-                self._probe_feat[phys] = torch.where(ok[:, None], self._ck_feat[slots], self._probe_feat[phys])
-        elif self.frame_stack or self.probes is not None:   # the resumed envs start a history of their own
+        ok, values = self._ledger.fetch(slots)      # ok: the envs the device does not reject
+        self._scatter(values, ok, envs)
+        # generic: stack rows and probe words came with the slot (and the feature rows with the ledger:
+        # an evaluation would pay reward), so no refill and no rebase; else the resumed envs start a
+        # history of their own
+        if not self._generic and (self.frame_stack or self.probes is not None):
             m = torch.zeros(self.emu.n, dtype=torch.uint8, device=self.device)
-            m[phys] = ok.to(torch.uint8)
+            m[self.phys(envs)] = ok.to(torch.uint8)
             self._machines_replaced(m)
 
     def fork(self, dst_envs, src_envs, check: bool = True):
@@ -655,8 +711,7 @@ class VecEnv:
         raises; check=True also rejects a destination that is a source of the same call."""
         dst = [int(e) for e in torch.as_tensor(dst_envs).reshape(-1).tolist()]
         src = [int(e) for e in torch.as_tensor(src_envs).reshape(-1).tolist()]
-        if self._ck_return is None:
-            raise RuntimeError("VecEnv(bank_episodes=True, fork_slots=...) forks envs")
+        self._require("fork")
         if len(dst) != len(src):
             raise ValueError("fork: dst_envs and src_envs must have the same length")
         if any(not 0 <= e < self.num_envs for e in dst + src):
@@ -685,12 +740,27 @@ class VecEnv:
         out[self._phys] = values
         return out
 
+    def _set_physical(self, buf: torch.Tensor, values: torch.Tensor):
+        """The reverse of _logical: a per-env tensor (env order) into the envs' rows of an emulator-order one."""
+        if self._padded:
+            buf[self._phys] = values
+        else:
+            buf.copy_(values)
+
+    def _take_keys(self, kind: str, frame, out: torch.Tensor | None = None, env0: int = 0, count: int | None = None):
+        """The keys of kind "ram", "frame" (frame = (bw, bh, levels)) or "frame+ram" — the second salted
+        with the first — of emulator envs [env0, env0 + count) into out (None: a new tensor), on the
+        current stream."""
+        salt = None
+        if kind != "frame":
+            salt = self.emu.cell_keys(self.archive_shift, out=out, env0=env0, count=count)
+            if kind == "ram":
+                return salt
+        return self.emu.frame_keys(*frame, salt=salt, out=out if salt is None else salt, env0=env0, count=count)
+
     def _cell_keys(self) -> torch.Tensor:
         """The keys archive_key names, in emulator order."""
-        if self.archive_key == "ram":
-            return self.emu.cell_keys(self.archive_shift)
-        salt = self.emu.cell_keys(self.archive_shift) if self.archive_key == "frame+ram" else None
-        return self.emu.frame_keys(*self.archive_frame, salt=salt, out=salt)
+        return self._take_keys(self.archive_key, self.archive_frame)
 
     def cell_keys(self) -> torch.Tensor:
         """The cell key of every env (int64, env order) as archive_key has it: pk_cell_keys with
@@ -713,8 +783,7 @@ class VecEnv:
         cell's new best episode is checkpointed into the cell's slot together with this class's
         episode return / length and start slot.  On the current stream after a pipeline join, like
         checkpoint_to_bank; no host sync.  Returns the slot each env won (int32, env order, -1 else)."""
-        if self._arch_out is None:
-            raise RuntimeError("VecEnv(archive_cells=...) keeps the archive")
+        self._require("archive")
         self._join_streams()
         scores = self._physical(self.stats.ep_return if scores is None else scores, float("nan"), torch.float64)
         keys = self._cell_keys() if keys is None else self._physical(keys, -1, torch.int64)
@@ -723,24 +792,14 @@ class VecEnv:
                               else torch.as_tensor(mask, device=self.device) != 0, 0, torch.uint8)
         self.emu.archive_update(keys, scores, mask, out=self._arch_out)
         won = self._logical(self._arch_out).long()
-        last = self._ck_return.numel() - 1
-        slots = torch.where(won >= 0, won, last)
-        self._ck_return[slots] = self.stats.ep_return
-        self._ck_length[slots] = self.stats.ep_length
-        self._ck_valid[slots] = True
-        self._ck_valid[last] = False
-        if self._ck_feat is not None:
-            self._ck_feat[slots] = self._logical(self._probe_feat)
-        if self._slots is not None:
-            self._ck_slots[slots] = self._logical(self._slots)
+        self._ledger.store(won, self._gather())
         return won.to(torch.int32)
 
     def archive_explore(self, mask) -> torch.Tensor:
         """Every env with mask[e] != 0 draws a cell (weight 1 / sqrt(visits + picks + 1)) and continues
         the episode kept there, as resume_from_bank does it; no host sync.  Returns the slot each
         env resumed from (int32, env order, -1 for the others and for rejects)."""
-        if self._arch_out is None:
-            raise RuntimeError("VecEnv(archive_cells=...) keeps the archive")
+        self._require("archive")
         self._join_streams()
         mask = self._physical(torch.as_tensor(mask, device=self.device) != 0, 0, torch.uint8)
         self.emu.archive_explore(mask, out=self._arch_out)
@@ -748,48 +807,38 @@ class VecEnv:
         if (self.frame_stack or self.probes is not None) and not self._generic:
             self._machines_replaced((self._arch_out >= 0).to(torch.uint8))
         drawn = self._logical(self._arch_out).long()
-        last = self._ck_return.numel() - 1
-        slots = torch.where(drawn >= 0, drawn, last)
-        ok = (drawn >= 0) & self._ck_valid[slots]
-        self.stats.ep_return.copy_(torch.where(ok, self._ck_return[slots], self.stats.ep_return))
-        self.stats.ep_length.copy_(torch.where(ok, self._ck_length[slots], self.stats.ep_length))
-        if self._ck_feat is not None:
-            feat = torch.where(ok[:, None], self._ck_feat[slots], self._logical(self._probe_feat))
-            if self._padded:
-                self._probe_feat[self._phys] = feat
-            else:
-                self._probe_feat.copy_(feat)
-        if self._slots is not None:
-            cur = self._logical(self._slots)
-            new = torch.where(ok, self._ck_slots[slots], cur)
-            if self._padded:
-                self._slots[self._phys] = new
-            else:
-                self._slots.copy_(new)
+        ok, values = self._ledger.fetch(drawn)      # ok: drawn >= 0 and the slot holds an episode
+        self._scatter(values, ok)
         return drawn.to(torch.int32)
 
+    _REQUIRES = {   # feature -> (the attribute that is None, False or 0 without it, what to say then)
+        "episodes": ("_ledger", "VecEnv(bank_episodes=True) keeps episode checkpoints"),
+        "fork": ("_ledger", "VecEnv(bank_episodes=True, fork_slots=...) forks envs"),
+        "archive": ("archive_cells", "VecEnv(archive_cells=...) keeps the archive"),
+        "exchange": ("archive_exchange", "VecEnv(archive_cells=..., archive_exchange=True) exchanges archive cells"),
+        "trajectories": ("record_trajectories", "VecEnv(record_trajectories=True) records trajectories"),
+        "novelty": ("novelty_log2", "VecEnv(novelty_log2=...) counts visits"),
+    }
+
+    def _require(self, feature: str):
+        """Raise unless the constructor was given what `feature` needs."""
+        attr, text = self._REQUIRES[feature]
+        if not getattr(self, attr):
+            raise RuntimeError(text)
+
     def _exchange(self):
-        if not self.archive_exchange:
-            raise RuntimeError("VecEnv(archive_cells=..., archive_exchange=True) exchanges archive cells")
+        self._require("exchange")
         self._join_streams()
 
     def _cell_rows(self) -> torch.Tensor:
-        """What this class keeps per slot, for the cells' slots: float64 (archive_cells, 4) rows of
-        _ck_return, _ck_length, _ck_valid, _ck_slots — row c travels with record c of a pack."""
-        sl = slice(self._arch0, self._arch0 + self.archive_cells)
-        return torch.stack([self._ck_return[sl], self._ck_length[sl], self._ck_valid[sl].to(torch.float64),
-                            self._ck_slots[sl].to(torch.float64)], dim=1)
+        """What this class keeps per slot, for the cells' slots: SlotLedger.rows — row c travels with
+        record c of a pack."""
+        return self._ledger.rows(self._arch0, self.archive_cells)
 
     def _place_rows(self, cell_out: torch.Tensor, rows: torch.Tensor):
         """Row i goes to the slot of cell cell_out[i]; the rows of records that won nothing go nowhere."""
-        last = self._ck_return.numel() - 1
         won = cell_out.long()
-        slots = torch.where(won >= 0, won + self._arch0, last)
-        self._ck_return[slots] = rows[:, 0]
-        self._ck_length[slots] = rows[:, 1]
-        self._ck_valid[slots] = rows[:, 2] != 0
-        self._ck_valid[last] = False
-        self._ck_slots[slots] = rows[:, 3].to(torch.int32)
+        self._ledger.place(torch.where(won >= 0, won + self._arch0, -1), rows)
 
     def archive_export(self) -> dict:
         """The whole archive as host arrays (a full pack, which changes nothing; synchronises):
@@ -831,8 +880,7 @@ class VecEnv:
         process group) is a no-op.  On the current stream after a pipeline join."""
         import torch.distributed as dist
         from .dist import archive_all_gather
-        if not self.archive_exchange:
-            raise RuntimeError("VecEnv(archive_cells=..., archive_exchange=True) exchanges archive cells")
+        self._require("exchange")
         if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
             return
         self._join_streams()
@@ -846,8 +894,7 @@ class VecEnv:
 
     def archive_state(self) -> dict:
         """The archive as host arrays (emu.archive_read; synchronous)."""
-        if self._arch_out is None:
-            raise RuntimeError("VecEnv(archive_cells=...) keeps the archive")
+        self._require("archive")
         return self.emu.archive_read()
 
     @staticmethod
@@ -863,8 +910,7 @@ class VecEnv:
         from origin and stepping through actions rebuilds the env exactly (False after load_state,
         load_from_bank, a RAM write, a reset that kept the machine, or a step past the capacity)}.
         Needs record_trajectories=True; waits for the sub-batch streams and syncs the host."""
-        if not self.record_trajectories:
-            raise RuntimeError("VecEnv(record_trajectories=True) records trajectories")
+        self._require("trajectories")
         self._join_streams()
         p = self.phys(int(env))
         g0 = p // 64 * 64
@@ -873,15 +919,13 @@ class VecEnv:
     def slot_trajectory(self, slot: int) -> dict:
         """trajectory() of the episode checkpointed in a bank slot; a slot that holds no episode is
         origin -1, no actions, not replayable."""
-        if not self.record_trajectories:
-            raise RuntimeError("VecEnv(record_trajectories=True) records trajectories")
+        self._require("trajectories")
         self._join_streams()
         return self._trajectory(self.emu.bank_trajectories(int(slot), 1), 0)
 
     def archive_trajectory(self, cell: int) -> dict:
         """trajectory() of the best episode the archive keeps for a cell."""
-        if self._arch_out is None:
-            raise RuntimeError("VecEnv(archive_cells=...) keeps the archive")
+        self._require("archive")
         if not 0 <= int(cell) < self.archive_cells:
             raise ValueError("archive_trajectory: no such cell")
         return self.slot_trajectory(self._arch0 + int(cell))
@@ -893,9 +937,14 @@ class VecEnv:
         """Emulator envs of sub-batch b."""
         return slice(b * self.slot, b * self.slot + self.batch_size)
 
-    def phys(self, env: int) -> int:
-        """Emulator index of env."""
+    def phys(self, env):
+        """Emulator index of env: sub-batch b lives in emulator envs [b * slot, b * slot + batch_size).
+        An int, or a tensor of env indices; the one place with this arithmetic (_env_of is its inverse)."""
         return (env // self.batch_size) * self.slot + env % self.batch_size
+
+    def _env_of(self, phys: int) -> int:
+        """The env at emulator index phys (not a padding env's)."""
+        return (phys // self.slot) * self.batch_size + phys % self.slot
 
     def _obs_buffer(self) -> torch.Tensor:
         """What the envs observe, in emulator order: the frame stack, the composite observation or the screen."""
@@ -925,8 +974,8 @@ class VecEnv:
             grows = _seen_cap_log2(mes) > self._cap_lg      # the seen set never shrinks
             self._cap_lg = max(self._cap_lg, _seen_cap_log2(mes))
             self.emu.set_episode_params(mes, rsc)
-            if grows and self._ck_return is not None and not self._generic:   # the device emptied every slot's episode part
-                self._ck_valid.zero_()
+            if grows and self._ledger is not None and not self._generic:   # the device emptied every slot's episode part
+                self._ledger.invalidate()
         if self._slots is None:
             obs = self._logical(self.emu.reset())
         else:
@@ -954,21 +1003,13 @@ class VecEnv:
             from ._native import ERR_EXCEPTIONS
             p = int(bad[0])
             code = int(codes[p])
-            e = (p // self.slot) * self.batch_size + p % self.slot
             codes.zero_()
             raise ERR_EXCEPTIONS.get(code, RuntimeError)(
-                f"env {e}: reference reward stack raises here (PK_ERR {code}); {bad.numel()} env(s) failed")
+                f"env {self._env_of(p)}: reference reward stack raises here (PK_ERR {code}); {bad.numel()} env(s) failed")
 
     def _novelty_take(self, psl: slice):
         """The keys of emulator envs psl into _nov_keys, on the current stream; no table is touched."""
-        env0, count = psl.start, psl.stop - psl.start
-        if self.novelty_key == "ram":
-            self.emu.cell_keys(self.archive_shift, out=self._nov_keys, env0=env0, count=count)
-            return
-        salt = None
-        if self.novelty_key == "frame+ram":
-            salt = self.emu.cell_keys(self.archive_shift, out=self._nov_keys, env0=env0, count=count)
-        self.emu.frame_keys(*self.novelty_frame, salt=salt, out=self._nov_keys, env0=env0, count=count)
+        self._take_keys(self.novelty_key, self.novelty_frame, self._nov_keys, psl.start, psl.stop - psl.start)
 
     def _novelty_count(self, psl: slice) -> torch.Tensor:
         """Count the keys taken for emulator envs psl (one table update, on the current stream);
@@ -987,8 +1028,7 @@ class VecEnv:
                 self._novelty_count(self._prange(b))
 
     def _novelty_last(self, t):
-        if t is None:
-            raise RuntimeError("VecEnv(novelty_log2=...) counts visits")
+        self._require("novelty")
         self._join_streams()
         return self._logical(t).clone()
 
@@ -1016,8 +1056,7 @@ class VecEnv:
         In a recv() / send() loop the sub-batches that are sent and not received yet are counted
         here, so that they travel with this call; their recv() returns the bonus all the same."""
         from .dist import counts_all_gather
-        if not self.novelty_log2:
-            raise RuntimeError("VecEnv(novelty_log2=...) counts visits")
+        self._require("novelty")
         if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
             return
         self._join_streams()

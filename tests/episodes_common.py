@@ -331,3 +331,93 @@ def check_fork(env, dev):
         assert torch.equal(env.stats.ep_length[dst], env.stats.ep_length[src]), t
         ended += int(term[dst].sum())
     assert ended == len(dst)                     # every forked episode ended inside the window
+
+
+def check_pool_slots(make, dev):
+    """VecEnv(48, batch_size=24, state_pool=two states, bank_slots=1, fork_slots=2, bank_episodes=True,
+    archive_cells=4) in padded 64-env slots: start_slots — with the episode return and length — of a
+    resumed, a forked and an explored env are the source's at its checkpoint, whichever sub-batch
+    either is in; every other env, a rejected one included, keeps its own; a save_to_bank over a
+    checkpointed slot makes the next resume from it a reject."""
+    from pokegym_amd.env import VecEnv
+    n, user = 48, 2                                  # slots: the pool's 0 and 1, the user's 2, fork 3-4, cells 5-8
+    seed = make(2)
+    seed.poke(0, 0xD361, bytes([2, 3]))
+    seed.poke(1, 0xD361, bytes([4, 5]))
+    pool = [seed.snapshot(0), seed.snapshot(1)]
+    seed.close()
+    emu = make(128, reward=True, reload_on_reset=True, max_episode_steps=1000)
+    env = VecEnv(n, emulator=emu, batch_size=24, log_interval=0, state_pool=pool, bank_slots=1, fork_slots=2,
+                 bank_episodes=True, archive_cells=4)
+    assert env._padded and emu.bank_slots == 9 and env._arch0 == 5
+    rng = np.random.default_rng(9)
+
+    def step():
+        env.emu.set_ram(0xD361, dev(rng.integers(0, 6, (emu.n, 2)), np.uint8))      # Script's walk: rewards differ
+        env.step(dev(rng.integers(0, 8, n), np.uint8))
+
+    def values():
+        return {"slot": env.start_slots.cpu().numpy().copy(), "ret": env.stats.ep_return.cpu().numpy().copy(),
+                "len": env.stats.ep_length.cpu().numpy().copy()}
+
+    def moved(before, mapping, at, what):
+        """Env d of mapping = {d: s} holds what env s held in record `at`, the others what they held before."""
+        after = values()
+        rest = [e for e in range(n) if e not in mapping]
+        for k in after:
+            assert after[k][list(mapping)].tobytes() == at[k][list(mapping.values())].tobytes(), (what, k)
+            assert after[k][rest].tobytes() == before[k][rest].tobytes(), (what, k, "the others keep theirs")
+
+    env.reset()
+    start = values()["slot"]
+    assert set(start.tolist()) == {0, 1}
+    zeros, ones = np.flatnonzero(start == 0), np.flatnonzero(start == 1)
+    step()
+    step()
+    # an env of the second sub-batch that started from slot 0, resumed over one of the first that started from 1
+    src, dst = int(zeros[zeros >= 24][0]), int(ones[ones < 24][0])
+    rejected = int(ones[ones < 24][1])
+    env.checkpoint_to_bank([src], [user])
+    ck = values()
+    step()
+    before = values()
+    assert before["len"][dst] == 3.0 and ck["len"][src] == 2.0 and before["ret"][dst] != ck["ret"][src]
+    env.resume_from_bank([dst, rejected], [user, 3])             # a scratch slot nothing was forked through yet
+    assert emu.bank_rejects() == 1
+    moved(before, {dst: src}, ck, "resume")
+    assert values()["slot"][dst] == 0 and values()["slot"][rejected] == 1
+    step()
+    # fork both ways: a source of slot 1 in the first sub-batch, the resumed env (slot 0, a step behind)
+    src1 = int(ones[ones < 24][2])
+    pairs = {int(zeros[zeros >= 24][1]): src1, int(ones[ones >= 24][0]): dst, int(zeros[zeros < 24][0]): src1}
+    before = values()
+    env.fork(list(pairs), list(pairs.values()))
+    assert emu.bank_rejects() == 0
+    moved(before, pairs, before, "fork")
+    assert [values()["slot"][d] for d in pairs] == [1, 0, 1] and [before["slot"][d] for d in pairs] == [0, 1, 0]
+    step()
+    # the archive: envs that started from slot 0 win every cell, envs that started from 1 explore
+    slots = values()["slot"]
+    before = values()
+    won = env.archive_update(scores=dev(rng.random(n) + (slots == 0), np.float64), keys=dev(np.arange(n) % 4, np.int64))
+    at_ck = values()
+    moved(before, {}, before, "update")
+    winner = {int(s): e for e, s in enumerate(won.cpu().numpy()) if s >= 0}
+    assert len(winner) == 4 and all(slots[e] == 0 for e in winner.values())
+    step()
+    now = values()["slot"]
+    explorers = [int(e) for half in (np.flatnonzero(now[:24] == 1)[:2], 24 + np.flatnonzero(now[24:] == 1)[:2]) for e in half]
+    assert len(explorers) == 4
+    before = values()
+    drawn = env.archive_explore(masked(explorers, dev, n)).cpu().numpy()
+    assert (drawn[explorers] >= 5).all() and (np.delete(drawn, explorers) == -1).all() and emu.bank_rejects() == 0
+    mapping = {e: winner[int(drawn[e])] for e in explorers}
+    moved(before, mapping, at_ck, "explore")
+    assert (values()["slot"][explorers] == 0).all() and (values()["len"][explorers] == at_ck["len"][list(mapping.values())]).all()
+    # a plain save over the checkpointed slot leaves it without an episode
+    before = values()
+    env.save_to_bank([0], [user])
+    env.resume_from_bank([rejected], [user])
+    assert emu.bank_rejects() == 1
+    moved(before, {}, before, "resume from a slot saved over")
+    emu.close()

@@ -529,6 +529,119 @@ def check_vecenv(make, dev):
     emu.close()
 
 
+def check_vecenv_padded(make, dev):
+    """VecEnv(48, batch_size=24, bank_episodes="generic", probe_features=True, frame_stack=2) in padded
+    64-env slots: a checkpoint of the second sub-batch resumed into the first (and a resume from an empty
+    slot), a fork both ways, an archive_update and an archive_explore.  After each of them probe_values,
+    the episode return and length and the stack rows of the touched envs are the source's at its
+    checkpoint, and their next step — fed the action the source took then — pays the source's reward
+    and leaves the source's values.  Every env no call has touched yet, the rejected one and the
+    neighbours of the touched ones among them, equals the same env of a twin that makes no bank call,
+    in all of that and at every step."""
+    from pokegym_amd.env import VecEnv
+    n = 48
+
+    def vecenv():
+        return VecEnv(n, emulator=make(N, reward=False, max_episode_steps=1000), batch_size=24, log_interval=0,
+                      reward=False, bank_episodes="generic", probes=P.pkbench_program(), probe_features=True,
+                      frame_stack=2, bank_slots=2, fork_slots=2, archive_cells=4, archive_key="frame")
+
+    env, twin = vecenv(), vecenv()
+    assert env._padded and env.emu.generic_parts == (PROBES | STACK)
+    acts = np.random.default_rng(43).integers(0, 8, (16, n)).astype(np.uint8)
+    touched = set()
+
+    def values(v):
+        return {"pv": v.probe_values.cpu().numpy().copy(), "ret": bits64(v.stats.ep_return.cpu().numpy()).copy(),
+                "len": v.stats.ep_length.cpu().numpy().copy(),
+                "stack": v._logical(v.emu.stack).reshape(n, -1).cpu().numpy().copy()}
+
+    def untouched(rec, other, what):
+        rest = sorted(set(range(n)) - touched)
+        same(rec, other, rest, rest, what)
+
+    def step(t, press=None):
+        """Step t of both, env d pressing press[d]: the actions, the rewards and the values after the step."""
+        a = acts[t].copy()
+        for d, action in (press or {}).items():
+            a[d] = action
+        rec = {"a": a, "rew": bits64(env.step(dev(a, np.uint8))[1].cpu().numpy()).copy(), **values(env)}
+        other = {"rew": bits64(twin.step(dev(acts[t], np.uint8))[1].cpu().numpy()), **values(twin)}
+        untouched({k: rec[k] for k in other}, other, ("the envs no call touched equal the twin's", t))
+        log[t] = rec
+        return rec
+
+    def moved(before, mapping, at, what):
+        """After a call: env d of mapping = {d: s} holds what env s held in record `at`, the others what
+        they held before the call; the neighbours of every d are among the others."""
+        after = values(env)
+        dst = list(mapping)
+        same(after, at, dst, [mapping[d] for d in dst], what)
+        rest = sorted(set(range(n)) - set(dst))
+        same(after, before, rest, rest, (what, "the others keep theirs"))
+        touched.update(dst)
+
+    def follows(t, mapping, u, what):
+        """Step t, the first after a call: env d of mapping = {d: s} continues as env s did at step u."""
+        rec = step(t, {d: log[u]["a"][s] for d, s in mapping.items()})
+        dst = list(mapping)
+        same(rec, log[u], dst, [mapping[d] for d in dst], what, keys=("rew", "pv", "ret", "len", "stack"))
+
+    log = {}
+    env.reset()
+    twin.reset()
+    for t in range(4):
+        step(t)
+    # a checkpoint of the second sub-batch, resumed two steps later into the first; slot 1 is empty
+    src, dst, rejected = 30, 5, 7
+    before = values(env)
+    env.checkpoint_to_bank([src], [0])
+    ck = values(env)
+    same(ck, before, range(n), range(n), "a checkpoint leaves every env as it is")
+    step(4)
+    step(5)
+    before = values(env)
+    assert not np.array_equal(before["stack"][dst], ck["stack"][src]) and before["len"][dst] != ck["len"][src]
+    env.resume_from_bank([dst, rejected], [0, 1])
+    assert env.emu.bank_rejects() == 1
+    moved(before, {dst: src}, ck, "resume")
+    assert values(env)["len"][dst] == 4.0
+    follows(6, {dst: src}, 4, "the step after the resume")
+    assert rejected not in touched                                       # step() compared it with the twin's
+    # a fork both ways; source 5 is two steps behind in its episode
+    pairs = {6: 29, 40: 5, 20: 29}
+    before = values(env)
+    assert before["len"][5] != before["len"][40]
+    env.fork(list(pairs), list(pairs.values()))
+    assert env.emu.bank_rejects() == 0
+    moved(before, pairs, before, "fork")
+    rec = step(7, {d: acts[7][s] for d, s in pairs.items()})
+    same(rec, rec, list(pairs), list(pairs.values()), "the step after the fork", keys=("rew", "pv", "ret", "len", "stack"))
+    # the archive: the winners' values at the update come back at the explore, two steps later
+    before = values(env)
+    won = env.archive_update().cpu().numpy()
+    at_ck = values(env)
+    same(at_ck, before, range(n), range(n), "an update leaves every env as it is")
+    winner = {int(s): e for e, s in enumerate(won) if s >= 0}
+    assert winner and all(env._arch0 <= s < env._arch0 + 4 for s in winner)
+    step(8)
+    step(9)
+    explorers = [4, 23, 24, 47]                                           # both ends of both sub-batches
+    mask = np.zeros(n, np.uint8)
+    mask[explorers] = 1
+    before = values(env)
+    drawn = env.archive_explore(dev(mask, np.uint8)).cpu().numpy()
+    assert (drawn[explorers] >= 0).all() and (np.delete(drawn, explorers) == -1).all() and env.emu.bank_rejects() == 0
+    mapping = {e: winner[int(drawn[e])] for e in explorers}
+    assert any(before["len"][e] != at_ck["len"][w] for e, w in mapping.items())
+    moved(before, mapping, at_ck, "explore")
+    follows(10, mapping, 8, "the step after the explore")
+    assert len({rec["stack"][e].tobytes() for e in range(n)}) > 8       # not a comparison of equal envs
+    assert len(set(log[10]["ret"].tolist())) > 4
+    env.emu.close()
+    twin.emu.close()
+
+
 def check_vecenv_errors(make, dev):
     """The constructor's rules; and a reward env with a frame stack still refills after a resume."""
     from pokegym_amd.env import VecEnv

@@ -101,3 +101,9 @@ def test_vecenv_fork():
     assert env.emu.n == 128 and env.emu.bank_slots == 4 and env.emu.bank_has_episodes
     ec.check_fork(env, dev)
     env.close()
+
+
+def test_vecenv_pool_slots_travel():
+    """Start slots, episode return and length through resume, fork and the archive in padded sub-batches."""
+    import episodes_common as ec
+    ec.check_pool_slots(make, dev)

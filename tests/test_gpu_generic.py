@@ -61,6 +61,11 @@ def test_vecenv():
     gc.check_vecenv(make, dev)
 
 
+def test_vecenv_padded_sub_batches():
+    import generic_common as gc
+    gc.check_vecenv_padded(make, dev)
+
+
 def test_vecenv_errors_and_the_old_refill():
     import generic_common as gc
     gc.check_vecenv_errors(make, dev)

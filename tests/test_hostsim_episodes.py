@@ -150,6 +150,12 @@ def test_vecenv_fork(monkeypatch):
     emu.close()
 
 
+def test_vecenv_pool_slots_travel(monkeypatch):
+    for name in ("Stream", "Event", "current_stream", "stream"):
+        monkeypatch.setattr(torch.cuda, name, _NoStream)
+    ec.check_pool_slots(make, dev)
+
+
 def test_vecenv_without_episodes_allocates_nothing():
     from pokegym_amd.env import VecEnv
     emu = make(4, reward=True)

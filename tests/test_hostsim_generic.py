@@ -65,6 +65,10 @@ def test_vecenv(no_streams):
     gc.check_vecenv(make, dev)
 
 
+def test_vecenv_padded_sub_batches(no_streams):
+    gc.check_vecenv_padded(make, dev)
+
+
 def test_vecenv_errors_and_the_old_refill(no_streams):
     gc.check_vecenv_errors(make, dev)
 
