@@ -359,6 +359,104 @@ struct pk_handle {
     bool prof = false;
     std::vector<hipEvent_t> ev_pool;
     size_t ev_used = 0;
+    // every device allocation of the handle (Stage::commit): what pk_destroy frees.  The typed fields
+    // above are the access path only
+    std::vector<void*> owned;
+};
+
+// ---- device memory: one owner, one staged allocation ---------------------------------------------
+//
+// A feature allocates through a Stage.  It names the buffers it wants — the handle field, the byte
+// count (0: none), a fill byte or a host source — and run() allocates them, fills or uploads them and
+// synchronises once.  Until commit() the handle is untouched: a failed run(), or a Stage that goes
+// out of scope, frees what was staged.  commit() publishes the pointers into the fields and the
+// owner; a field that held a buffer gives it up (it leaves the owner and is freed), which is how the
+// grow path of pk_set_episode_params replaces its buffers.  So a new feature stages, runs, does
+// whatever else can fail, commits, and only then sets the field that says it is there.
+class Stage {
+  public:
+    explicit Stage(pk_handle* h) : h_(h) {}
+    Stage(const Stage&) = delete;
+    Stage& operator=(const Stage&) = delete;
+    ~Stage() { drop(); }
+
+    template <class T>
+    void want(T*& field, size_t bytes, int fill_byte = -1, const void* src = nullptr) {
+        if (!bytes) return;
+        reqs_.push_back(Req{(void**)&field, nullptr, bytes});
+        if (fill_byte >= 0 || src) ops_.push_back(Op{(void**)&field, 0, bytes, fill_byte, src});
+    }
+    // further work on a part of a wanted buffer, in the order given
+    template <class T>
+    void fill(T*& field, size_t off, size_t bytes, int byte) { ops_.push_back(Op{(void**)&field, off, bytes, byte, nullptr}); }
+    template <class T>
+    void upload(T*& field, const void* src, size_t bytes) { ops_.push_back(Op{(void**)&field, 0, bytes, -1, src}); }
+
+    // the buffer staged for a field (null: none)
+    template <class T>
+    T* staged(T*& field) const {
+        for (const Req& r : reqs_)
+            if (r.dst == (void**)&field) return (T*)r.p;
+        return nullptr;
+    }
+
+    // what was asked for since the last run(); on failure everything staged so far is freed, the
+    // sticky error cleared, and oom / failed_bytes say whether and which allocation it was
+    hipError_t run() {
+        hipError_t e = hipSuccess;
+        oom = false;
+        for (; ran_ < reqs_.size() && e == hipSuccess; ran_++) {
+            Req& r = reqs_[ran_];
+            e = hipMalloc(&r.p, r.bytes);
+            if (e != hipSuccess) { r.p = nullptr; oom = true; failed_bytes = r.bytes; }
+        }
+        for (const Op& o : ops_) {
+            if (e != hipSuccess) break;
+            uint8_t* p = nullptr;
+            for (const Req& r : reqs_)
+                if (r.dst == o.dst) p = (uint8_t*)r.p + o.off;
+            e = o.src ? hipMemcpy(p, o.src, o.bytes, hipMemcpyHostToDevice) : hipMemset(p, o.byte, o.bytes);
+        }
+        ops_.clear();
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) {
+            drop();
+            (void)hipGetLastError();
+        }
+        return e;
+    }
+
+    void commit() {
+        for (const Req& r : reqs_) {
+            if (*r.dst) {
+                for (void*& q : h_->owned)
+                    if (q == *r.dst) { q = h_->owned.back(); h_->owned.pop_back(); break; }
+                (void)hipFree(*r.dst);
+            }
+            *r.dst = r.p;
+            h_->owned.push_back(r.p);
+        }
+        reqs_.clear();
+        ran_ = 0;
+    }
+
+    bool oom = false;
+    size_t failed_bytes = 0;
+
+  private:
+    struct Req { void** dst; void* p; size_t bytes; };
+    struct Op { void** dst; size_t off, bytes; int byte; const void* src; };
+    void drop() {
+        for (const Req& r : reqs_)
+            if (r.p) (void)hipFree(r.p);
+        reqs_.clear();
+        ops_.clear();
+        ran_ = 0;
+    }
+    pk_handle* h_;
+    std::vector<Req> reqs_;
+    std::vector<Op> ops_;
+    size_t ran_ = 0;
 };
 
 static int prof_event(pk_handle* h, hipStream_t s) {
@@ -391,15 +489,7 @@ void pk_destroy(pk_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
-    void* ptrs[] = {h->mem, h->regs, h->lat, h->screen, h->rom, h->ucode, h->bank_slot, h->slot_bank, h->t_mem, h->t_regs,
-                    h->t_lat, h->t_screen, h->scratch, h->rs, h->rsd, h->seen, h->mask, h->cutc, h->obs, h->reload,
-                    h->lists, h->dbg, h->info, h->info_flag, h->heat, h->info_bits, h->bank_slot_s, h->slot_bank_s,
-                    h->b_mem, h->b_regs, h->b_lat, h->b_screen, h->b_filled, h->b_rejects, h->b_lists, h->b_src,
-                    h->e_fields, h->e_seen, h->e_mask, h->e_cutc, h->b_ep_filled, h->a_fix, h->a_ones, h->a_zero,
-                    h->x_fix, h->x_ones, h->x_zero, h->t_act, h->t_origin, h->t_flags, h->bt_act, h->bt_origin, h->bt_flags,
-                    h->c_fix, h->fs_stack, h->pr_prog, h->pr_state, h->g_regs, h->g_probe, h->g_stack};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
+    for (void* p : h->owned) (void)hipFree(p);
     delete h;
 }
 
@@ -482,55 +572,11 @@ int pk_create(const pk_config* cfg, pk_handle** out) {
     } else {
         power_on(h->tmpl);
     }
-#define ALLOC(ptr, bytes)                                                                  \
-    do {                                                                                   \
-        hipError_t e_ = hipMalloc((void**)&(ptr), (bytes));                                \
-        if (e_ != hipSuccess) {                                                            \
-            pk_destroy(h);                                                                 \
-            return fail(-ENOMEM, "hipMalloc(%zu): %s", (size_t)(bytes), hipGetErrorString(e_)); \
-        }                                                                                  \
-    } while (0)
     if (hipSetDevice(h->device) != hipSuccess) { delete h; return fail(-ENODEV, "hipSetDevice(%d) failed", cfg->device); }
-    ALLOC(h->mem, (size_t)h->ngroups * PK_GROUP_STRIDE);
-    ALLOC(h->regs, (size_t)PK_NREGS * h->npad * 4);
-    ALLOC(h->lat, 3 * h->lat_stride * 4);
-    ALLOC(h->screen, (size_t)h->npad * PK_SCREEN);
-    ALLOC(h->rom, cfg->rom_len + 16);
-    ALLOC(h->ucode, PK_UC_WORDS * 4);
-    ALLOC(h->bank_slot, 128);
-    ALLOC(h->slot_bank, PK_LDS_SLOTS);
-    ALLOC(h->bank_slot_s, 128);
-    ALLOC(h->slot_bank_s, PK_SMALL_LDS_SLOTS);
-    ALLOC(h->t_mem, PK_PHYS);
-    ALLOC(h->t_regs, PK_NREGS * 4);
-    ALLOC(h->t_lat, 3 * PK_ROWS * 4);
-    ALLOC(h->t_screen, PK_SCREEN);
-    ALLOC(h->scratch, PK_PHYS + PK_NREGS * 4 + 3 * PK_ROWS * 4 + PK_SCREEN);
-    ALLOC(h->lists, (2 * (size_t)h->ngroups + 2 * (size_t)h->npad) * 4);
-#if defined(PK_STAMP) || defined(PK_WAVETIME)
-    ALLOC(h->dbg, PK_DBG_WORDS * 8);
-    (void)hipMemset(h->dbg, 0, PK_DBG_WORDS * 8);
-#endif
-    if (h->flags & PK_F_REWARD) {
-        ALLOC(h->rs, (size_t)RS_NFIELDS * h->npad * 4);
-        ALLOC(h->rsd, (size_t)RSD_NFIELDS * h->npad * 8);
-        ALLOC(h->seen, (size_t)h->npad * (1ull << h->cap_log2) * 4);
-        ALLOC(h->mask, (size_t)h->npad * PK_MASK_WORDS * 4);
-        ALLOC(h->cutc, (size_t)h->npad * PK_CUTC_CAP * 4);
-        ALLOC(h->obs, (size_t)h->npad * PK_OBS_BYTES);
-        ALLOC(h->reload, h->npad);
-        ALLOC(h->info, (size_t)PK_INFO_NFIELDS * h->npad * 8);
-        ALLOC(h->info_flag, h->npad);
-        ALLOC(h->info_bits, (size_t)PK_INFO_BITS_WORDS * h->npad * 4);
-        if (h->flags & PK_F_HEATMAP) ALLOC(h->heat, (size_t)h->npad * PK_HEAT_ROWS * PK_HEAT_COLS * 4);
-    }
-#undef ALLOC
     std::vector<uint32_t> uc(PK_UC_WORDS);
     pk_build_ucode(uc.data());
-    hipError_t e = hipSuccess;
-    if (e == hipSuccess) e = hipMemset(h->rom + cfg->rom_len, 0xFF, 16);
-    if (e == hipSuccess) e = hipMemcpy(h->rom, cfg->rom, cfg->rom_len, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(h->ucode, uc.data(), uc.size() * 4, hipMemcpyHostToDevice);
+    int8_t bs[128], bs_s[128];
+    uint8_t sb[PK_LDS_SLOTS] = {0};
     {
         // ROM banks staged in LDS by the step kernel: bank 0, then the switchable banks that hold
         // code or data, in bank order (a bank of one repeated byte — an unused bank of the
@@ -563,43 +609,58 @@ int pk_create(const pk_config* cfg, pk_handle** out) {
         if (want < 1) want = 1;
         if (want > PK_LDS_SLOTS) want = PK_LDS_SLOTS;
         if (want > nb) want = nb;
-        int8_t bs[128];
-        uint8_t sb[PK_LDS_SLOTS] = {0};
         memset(bs, -1, sizeof bs);
         for (uint32_t k = 0; k < want; k++) { sb[k] = (uint8_t)order[k]; bs[order[k]] = (int8_t)k; }
         h->nslots = want;
-        if (e == hipSuccess) e = hipMemcpy(h->bank_slot, bs, sizeof bs, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(h->slot_bank, sb, sizeof sb, hipMemcpyHostToDevice);
         // the small-LDS kernel stages the first PK_SMALL_LDS_SLOTS of the same banks
         h->nslots_s = want < PK_SMALL_LDS_SLOTS ? want : PK_SMALL_LDS_SLOTS;
-        for (uint32_t k = h->nslots_s; k < want; k++) bs[order[k]] = -1;
-        if (e == hipSuccess) e = hipMemcpy(h->bank_slot_s, bs, sizeof bs, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(h->slot_bank_s, sb, PK_SMALL_LDS_SLOTS, hipMemcpyHostToDevice);
+        memcpy(bs_s, bs, sizeof bs);
+        for (uint32_t k = h->nslots_s; k < want; k++) bs_s[order[k]] = -1;
     }
-    if (e == hipSuccess) e = hipMemcpy(h->t_mem, h->tmpl.mem.data(), PK_PHYS, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(h->t_regs, h->tmpl.regs, sizeof h->tmpl.regs, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(h->t_lat, h->tmpl.lat, sizeof h->tmpl.lat, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(h->t_screen, h->tmpl.screen.data(), PK_SCREEN, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(h->regs, 0, (size_t)PK_NREGS * h->npad * 4);
-    if (e == hipSuccess) e = hipMemset(h->lat, 0, 3 * h->lat_stride * 4);
+    Stage st(h);
+    st.want(h->mem, (size_t)h->ngroups * PK_GROUP_STRIDE);
+    st.want(h->regs, (size_t)PK_NREGS * h->npad * 4, 0);
+    st.want(h->lat, 3 * h->lat_stride * 4, 0);
+    st.want(h->screen, (size_t)h->npad * PK_SCREEN);
+    st.want(h->rom, cfg->rom_len + 16);
+    st.fill(h->rom, cfg->rom_len, 16, 0xFF);
+    st.upload(h->rom, cfg->rom, cfg->rom_len);
+    st.want(h->ucode, PK_UC_WORDS * 4, -1, uc.data());
+    st.want(h->bank_slot, 128, -1, bs);
+    st.want(h->slot_bank, PK_LDS_SLOTS, -1, sb);
+    st.want(h->bank_slot_s, 128, -1, bs_s);
+    st.want(h->slot_bank_s, PK_SMALL_LDS_SLOTS, -1, sb);
+    st.want(h->t_mem, PK_PHYS, -1, h->tmpl.mem.data());
+    st.want(h->t_regs, PK_NREGS * 4, -1, h->tmpl.regs);
+    st.want(h->t_lat, 3 * PK_ROWS * 4, -1, h->tmpl.lat);
+    st.want(h->t_screen, PK_SCREEN, -1, h->tmpl.screen.data());
+    st.want(h->scratch, PK_PHYS + PK_NREGS * 4 + 3 * PK_ROWS * 4 + PK_SCREEN);
+    st.want(h->lists, (2 * (size_t)h->ngroups + 2 * (size_t)h->npad) * 4);
+#if defined(PK_STAMP) || defined(PK_WAVETIME)
+    st.want(h->dbg, PK_DBG_WORDS * 8, 0);
+#endif
     if (h->flags & PK_F_REWARD) {
         // nothing has been reset yet (reset_count 0); update_heat_map's last_map = -1 (:462)
-        if (e == hipSuccess) e = hipMemset(h->rs, 0, (size_t)RS_NFIELDS * h->npad * 4);
-        if (e == hipSuccess) e = hipMemset(h->rs + (size_t)RS_HEAT_LAST * h->npad, 0xFF, (size_t)h->npad * 4);
-        if (e == hipSuccess) e = hipMemset(h->rs + (size_t)RS_MASK_MAP * h->npad, 0xFF, (size_t)h->npad * 4);
-        if (e == hipSuccess) e = hipMemset(h->rsd, 0, (size_t)RSD_NFIELDS * h->npad * 8);
-        if (e == hipSuccess) e = hipMemset(h->seen, 0, (size_t)h->npad * (1ull << h->cap_log2) * 4);
-        if (e == hipSuccess) e = hipMemset(h->mask, 0, (size_t)h->npad * PK_MASK_WORDS * 4);
-        if (e == hipSuccess) e = hipMemset(h->obs, 0, (size_t)h->npad * PK_OBS_BYTES);
-        if (e == hipSuccess) e = hipMemset(h->info, 0, (size_t)PK_INFO_NFIELDS * h->npad * 8);
-        if (e == hipSuccess) e = hipMemset(h->info_flag, 0, h->npad);
-        if (e == hipSuccess) e = hipMemset(h->info_bits, 0, (size_t)PK_INFO_BITS_WORDS * h->npad * 4);
-        if (e == hipSuccess && h->heat) e = hipMemset(h->heat, 0, (size_t)h->npad * PK_HEAT_ROWS * PK_HEAT_COLS * 4);
+        st.want(h->rs, (size_t)RS_NFIELDS * h->npad * 4, 0);
+        st.fill(h->rs, (size_t)RS_HEAT_LAST * h->npad * 4, (size_t)h->npad * 4, 0xFF);
+        st.fill(h->rs, (size_t)RS_MASK_MAP * h->npad * 4, (size_t)h->npad * 4, 0xFF);
+        st.want(h->rsd, (size_t)RSD_NFIELDS * h->npad * 8, 0);
+        st.want(h->seen, (size_t)h->npad * (1ull << h->cap_log2) * 4, 0);
+        st.want(h->mask, (size_t)h->npad * PK_MASK_WORDS * 4, 0);
+        st.want(h->cutc, (size_t)h->npad * PK_CUTC_CAP * 4);
+        st.want(h->obs, (size_t)h->npad * PK_OBS_BYTES, 0);
+        st.want(h->reload, h->npad);
+        st.want(h->info, (size_t)PK_INFO_NFIELDS * h->npad * 8, 0);
+        st.want(h->info_flag, h->npad, 0);
+        st.want(h->info_bits, (size_t)PK_INFO_BITS_WORDS * h->npad * 4, 0);
+        if (h->flags & PK_F_HEATMAP) st.want(h->heat, (size_t)h->npad * PK_HEAT_ROWS * PK_HEAT_COLS * 4, 0);
     }
-    if (e != hipSuccess) {
-        pk_destroy(h);
+    if (hipError_t e = st.run()) {
+        delete h;
+        if (st.oom) return fail(-ENOMEM, "hipMalloc(%zu): %s", st.failed_bytes, hipGetErrorString(e));
         return fail(-EIO, "device upload failed: %s", hipGetErrorString(e));
     }
+    st.commit();
     if ((rc = template_reset(h, nullptr, 0, h->n, nullptr))) { pk_destroy(h); return rc; }
     if (hipDeviceSynchronize() != hipSuccess) { pk_destroy(h); return fail(-EIO, "initial reset failed"); }
     *out = h;
@@ -626,6 +687,16 @@ static uint32_t* list_ids(pk_handle* h, uint32_t env0, int which) {
     return h->lists + 2u * h->ngroups + (size_t)which * h->npad + env0;
 }
 
+// the template reload of the envs of [env0, env1) that the range's reset list names
+static PkResetArgs reset_args(pk_handle* h, uint32_t env0, uint32_t env1) {
+    PkResetArgs a;
+    a.mem = h->mem; a.regs = h->regs; a.lat = h->lat; a.screen = h->screen;
+    a.tmpl_mem = h->t_mem; a.tmpl_regs = h->t_regs; a.tmpl_lat = h->t_lat; a.tmpl_screen = h->t_screen;
+    a.cnt = list_cnt(h, env0, 0); a.ids = list_ids(h, env0, 0); a.n = h->n; a.npad = h->npad;
+    a.lat_stride = (uint32_t)h->lat_stride; a.env0 = env0; a.env1 = env1; a.ilv_sh = h->ilv_sh;
+    return a;
+}
+
 // reload the template state (regs, RAM image, latches, screen) into the masked envs of [env0, env1):
 // the envs are listed on the device first, so the reset costs in proportion to the envs it touches
 static int template_reset(pk_handle* h, const uint8_t* mask, uint32_t env0, uint32_t env1, void* stream) {
@@ -633,12 +704,7 @@ static int template_reset(pk_handle* h, const uint8_t* mask, uint32_t env0, uint
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipMemsetAsync(list_cnt(h, env0, 0), 0, 4, s));
     HIPCHK(pk_launch_list(mask, env0, env1, list_cnt(h, env0, 0), list_ids(h, env0, 0), s));
-    PkResetArgs a;
-    a.mem = h->mem; a.regs = h->regs; a.lat = h->lat; a.screen = h->screen;
-    a.tmpl_mem = h->t_mem; a.tmpl_regs = h->t_regs; a.tmpl_lat = h->t_lat; a.tmpl_screen = h->t_screen;
-    a.cnt = list_cnt(h, env0, 0); a.ids = list_ids(h, env0, 0); a.n = h->n; a.npad = h->npad;
-    a.lat_stride = (uint32_t)h->lat_stride; a.env0 = env0; a.env1 = env1; a.ilv_sh = h->ilv_sh;
-    HIPCHK(pk_launch_reset(a, s));
+    HIPCHK(pk_launch_reset(reset_args(h, env0, env1), s));
     return 0;
 }
 
@@ -687,86 +753,30 @@ static int traj_mark(pk_handle* h, const uint32_t* cnt, const uint32_t* ids, uin
     return 0;
 }
 
-// one set of trajectory parts: rows of cap bytes with an origin and a flag word each
-struct TrajBufs {
-    uint8_t* act = nullptr;
-    int32_t* origin = nullptr;
-    uint32_t* flags = nullptr;
-};
-
-static void traj_free(TrajBufs& b) {
-    void* ptrs[] = {b.act, b.origin, b.flags};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    b = TrajBufs();
-}
-
-// rows zeroed, origins -1, flags as given (one word per row); all or nothing
-static int traj_alloc(size_t rows, uint32_t cap, const std::vector<uint32_t>& flags, TrajBufs& b) {
-    hipError_t e = hipMalloc((void**)&b.act, rows * cap);
-    if (e == hipSuccess) e = hipMalloc((void**)&b.origin, rows * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&b.flags, rows * 4);
-    if (e == hipSuccess) e = hipMemset(b.act, 0, rows * cap);
-    if (e == hipSuccess) e = hipMemset(b.origin, 0xFF, rows * 4);
-    if (e == hipSuccess) e = hipMemcpy(b.flags, flags.data(), rows * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
+// stages one set of trajectory parts for the three fields given: rows of cap bytes zeroed, an
+// origin of -1 and a flag word as given per row
+static int traj_stage(Stage& st, uint8_t*& act, int32_t*& origin, uint32_t*& flags, size_t rows, uint32_t cap,
+                      const std::vector<uint32_t>& row_flags) {
+    st.want(act, rows * cap, 0);
+    st.want(origin, rows * 4, 0xFF);
+    st.want(flags, rows * 4, -1, row_flags.data());
+    const hipError_t e = st.run();
     if (e == hipSuccess) return 0;
-    traj_free(b);
-    (void)hipGetLastError();
     return fail(-ENOMEM, "trajectories of %zu rows of %u bytes: %s", rows, cap, hipGetErrorString(e));
+}
+static int traj_stage_envs(Stage& st, pk_handle* h, uint32_t cap, const std::vector<uint32_t>& row_flags) {
+    return traj_stage(st, h->t_act, h->t_origin, h->t_flags, h->npad, cap, row_flags);
+}
+static int traj_stage_slots(Stage& st, pk_handle* h, uint32_t cap, uint32_t flag) {
+    return traj_stage(st, h->bt_act, h->bt_origin, h->bt_flags, h->bank_n, cap, std::vector<uint32_t>(h->bank_n, flag));
 }
 
 static uint32_t traj_cap_of(uint32_t cap_log2) { return 3u << (cap_log2 - 2u); }
 
-// the trajectory parts of a seen set grown to 1 << need: new rows for the envs, every one flagged
-// PK_TRAJ_BROKEN (its actions stay behind), and for the slots where the bank has them (their
-// episode parts are emptied by the caller; generic parts stay, so those rows are flagged too)
-static int traj_grow_alloc(pk_handle* h, uint32_t need, TrajBufs& envs, TrajBufs& slots) {
-    if (!h->traj_cap) return 0;
-    int rc = traj_alloc(h->npad, traj_cap_of(need), std::vector<uint32_t>(h->npad, PK_TRAJ_BROKEN), envs);
-    if (!rc && h->bt_act && (rc = traj_alloc(h->bank_n, traj_cap_of(need),
-                                          std::vector<uint32_t>(h->bank_n, h->gep_parts ? PK_TRAJ_BROKEN : 0u), slots)))
-        traj_free(envs);
-    return rc;
-}
-
-static void traj_grow_commit(pk_handle* h, uint32_t need, TrajBufs& envs, TrajBufs& slots) {
-    if (!h->traj_cap) return;
-    TrajBufs old_e, old_s;
-    old_e.act = h->t_act; old_e.origin = h->t_origin; old_e.flags = h->t_flags;
-    old_s.act = h->bt_act; old_s.origin = h->bt_origin; old_s.flags = h->bt_flags;
-    traj_free(old_e);
-    h->t_act = envs.act; h->t_origin = envs.origin; h->t_flags = envs.flags;
-    if (slots.act) {
-        traj_free(old_s);
-        h->bt_act = slots.act; h->bt_origin = slots.origin; h->bt_flags = slots.flags;
-    }
-    h->traj_cap = traj_cap_of(need);
-}
+static int reset_envs(pk_handle* h, uint32_t env0, uint32_t count, const uint8_t* mask, const int32_t* slots, void* stream);
 
 int pk_reset_range(pk_handle* h, uint32_t env0, uint32_t count, const uint8_t* mask, void* stream) {
-    int rc;
-    if ((rc = check_range(h, env0, count))) return rc;
-    const uint32_t env1 = env0 + count;
-    if (!(h->flags & PK_F_REWARD)) {
-        if ((rc = template_reset(h, mask, env0, env1, stream))) return rc;
-        return traj_reset(h, mask, nullptr, nullptr, env0, env1, (hipStream_t)stream);
-    }
-    HIPCHK(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    PkRewardArgs r = reward_args(h, env0, env1);
-    r.env_mask = mask;
-    HIPCHK(pk_launch_rreset_pre(r, s));
-    if ((rc = template_reset(h, h->reload, env0, env1, stream))) return rc;
-    HIPCHK(pk_launch_rreset_post(r, s));
-    if ((rc = traj_reset(h, mask, h->reload, nullptr, env0, env1, s))) return rc;
-    // the observation of the reset envs only (list of the masked envs)
-    HIPCHK(hipMemsetAsync(list_cnt(h, env0, 1), 0, 4, s));
-    HIPCHK(pk_launch_list(mask, env0, env1, list_cnt(h, env0, 1), list_ids(h, env0, 1), s));
-    r.ocnt = list_cnt(h, env0, 1);
-    r.oids = list_ids(h, env0, 1);
-    HIPCHK(pk_launch_obs(r, s));
-    return 0;
+    return reset_envs(h, env0, count, mask, nullptr, stream);
 }
 
 int pk_reset(pk_handle* h, const uint8_t* mask, void* stream) {
@@ -975,8 +985,12 @@ int pk_snapshot_range(pk_handle* h, uint32_t env0, uint32_t count, uint8_t* out,
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipDeviceSynchronize());
     const uint32_t chunk = count < 1024u ? count : 1024u;
+    // the call's own gather buffer: staged and never committed, so it goes with the Stage
+    Stage tmp(h);
     uint8_t* dmem = nullptr;
-    HIPCHK(hipMalloc((void**)&dmem, (size_t)chunk * PK_PHYS));
+    tmp.want(dmem, (size_t)chunk * PK_PHYS);
+    if (hipError_t e = tmp.run()) return fail(-EIO, "pk_snapshot_range: %s", hipGetErrorString(e));
+    dmem = tmp.staged(dmem);
     std::vector<uint8_t> mem((size_t)chunk * PK_PHYS), screen((size_t)chunk * PK_SCREEN);
     std::vector<uint32_t> regs((size_t)PK_NREGS * chunk), latg;
     int rc = 0;
@@ -1005,7 +1019,6 @@ int pk_snapshot_range(pk_handle* h, uint32_t env0, uint32_t count, uint8_t* out,
             export_v9(h->tmpl, r, &mem[(size_t)i * PK_PHYS], lat, &screen[(size_t)i * PK_SCREEN], out + (size_t)(c0 + i) * S_SIZE);
         }
     }
-    (void)hipFree(dmem);
     return rc;
 }
 
@@ -1172,53 +1185,46 @@ int pk_set_episode_params(pk_handle* h, uint32_t max_episode_steps, double rewar
     HIPCHK(hipSetDevice(h->device));
     uint32_t need = 10;
     while ((1ull << need) * 3 < ((uint64_t)max_episode_steps + 2) * 4) need++;
-    // the trajectory rows follow the seen set's capacity: allocated first, committed last
-    TrajBufs tj_envs, tj_slots;
-    if (h->flags & PK_F_REWARD) {
-        if (need > h->cap_log2) {
-            HIPCHK(hipDeviceSynchronize());
-            int rc = traj_grow_alloc(h, need, tj_envs, tj_slots);
-            if (rc) return rc;
-            auto drop = [&]() { traj_free(tj_envs); traj_free(tj_slots); };
-            uint32_t* seen = nullptr;
+    // with the reward stack the seen set grows; the trajectory rows follow its capacity, or without
+    // a seen set keep cap >= max_episode_steps alone.  Everything new is staged and replaces the old
+    // buffers at the commit, so a failure leaves the handle as it was
+    if (need > h->cap_log2 && ((h->flags & PK_F_REWARD) || h->traj_cap)) {
+        HIPCHK(hipDeviceSynchronize());
+        Stage st(h);
+        int rc;
+        // new rows for the envs, every one flagged PK_TRAJ_BROKEN (its actions stay behind), and for
+        // the slots where the bank has them (their episode parts are emptied below; generic parts
+        // stay, so those rows are flagged too)
+        if (h->traj_cap && (rc = traj_stage_envs(st, h, traj_cap_of(need), std::vector<uint32_t>(h->npad, PK_TRAJ_BROKEN))))
+            return rc;
+        if (h->traj_cap && h->bt_act && (rc = traj_stage_slots(st, h, traj_cap_of(need), h->gep_parts ? PK_TRAJ_BROKEN : 0u)))
+            return rc;
+        if (h->flags & PK_F_REWARD) {
             const size_t bytes = (size_t)h->npad * (1ull << need) * 4;
-            if (hipMalloc((void**)&seen, bytes) != hipSuccess) { drop(); return fail(-ENOMEM, "hipMalloc(%zu) for the seen set", bytes); }
-            if (hipMemset(seen, 0, bytes) != hipSuccess) { (void)hipFree(seen); drop(); return fail(-EIO, "hipMemset failed"); }
-            hipError_t e = pk_launch_seen_rehash(h->seen, h->cap_log2, seen, need, h->rs, h->n, h->npad, nullptr);
+            st.want(h->seen, bytes, 0);
+            if (st.run() != hipSuccess)
+                return st.oom ? fail(-ENOMEM, "hipMalloc(%zu) for the seen set", bytes) : fail(-EIO, "hipMemset failed");
+            hipError_t e = pk_launch_seen_rehash(h->seen, h->cap_log2, st.staged(h->seen), need, h->rs, h->n, h->npad, nullptr);
             if (e == hipSuccess) e = hipDeviceSynchronize();
-            if (e != hipSuccess) { (void)hipFree(seen); drop(); return fail(-EIO, "seen-set rehash: %s", hipGetErrorString(e)); }
+            if (e != hipSuccess) return fail(-EIO, "seen-set rehash: %s", hipGetErrorString(e));
             if (h->b_ep_filled) {
                 // the slots' seen tables follow the envs' size: reallocated, and every episode part
                 // marked empty (a resume from an older checkpoint is then a reject)
-                uint32_t* eseen = nullptr;
                 const size_t eb = (size_t)h->bank_n * (1ull << need) * 4;
-                e = hipMalloc((void**)&eseen, eb);
-                if (e == hipSuccess) e = hipMemset(eseen, 0, eb);
+                st.want(h->e_seen, eb, 0);
+                e = st.run();
                 if (e == hipSuccess) e = hipMemset(h->b_ep_filled, 0, h->bank_n);
                 if (e == hipSuccess) e = hipDeviceSynchronize();
                 if (e != hipSuccess) {
-                    if (eseen) (void)hipFree(eseen);
-                    (void)hipFree(seen);
-                    drop();
                     (void)hipGetLastError();
                     return fail(-ENOMEM, "episode parts of %u slots at the larger seen set (%zu bytes): %s", h->bank_n, eb,
                                 hipGetErrorString(e));
                 }
-                (void)hipFree(h->e_seen);
-                h->e_seen = eseen;
             }
-            (void)hipFree(h->seen);
-            h->seen = seen;
-            h->cap_log2 = need;
-            traj_grow_commit(h, need, tj_envs, tj_slots);
         }
-    } else if (h->traj_cap && need > h->cap_log2) {
-        // no seen set to follow: the rows alone keep cap >= max_episode_steps
-        HIPCHK(hipDeviceSynchronize());
-        int rc = traj_grow_alloc(h, need, tj_envs, tj_slots);
-        if (rc) return rc;
+        st.commit();
         h->cap_log2 = need;
-        traj_grow_commit(h, need, tj_envs, tj_slots);
+        if (h->traj_cap) h->traj_cap = traj_cap_of(need);
     }
     h->max_steps = max_episode_steps;
     h->reward_scale = reward_scale;
@@ -1264,17 +1270,9 @@ int pk_launch_shape(pk_handle* h, uint32_t env0, uint32_t count, uint32_t* out5)
 
 // ---- savestate bank -------------------------------------------------------------------------
 
-static void bank_free(pk_handle* h) {
-    void* ptrs[] = {h->b_mem, h->b_regs, h->b_lat, h->b_screen, h->b_filled, h->b_rejects, h->b_lists, h->b_src,
-                    h->e_fields, h->e_seen, h->e_mask, h->e_cutc, h->b_ep_filled};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    h->e_fields = h->e_seen = h->e_mask = h->e_cutc = nullptr;
-    h->b_ep_filled = nullptr;
-    h->b_mem = h->b_screen = h->b_filled = nullptr;
-    h->b_regs = h->b_lat = h->b_rejects = h->b_lists = nullptr;
-    h->b_src = nullptr;
-    h->bank_n = 0;
+static int require_bank(const pk_handle* h) {
+    if (!h->bank_n) return fail(-ENOENT, "the handle has no bank (pk_bank_create)");
+    return 0;
 }
 
 int pk_bank_create(pk_handle* h, uint32_t n_slots) {
@@ -1283,29 +1281,22 @@ int pk_bank_create(pk_handle* h, uint32_t n_slots) {
     if (n_slots == 0 || n_slots > PK_BANK_MAX_SLOTS) return fail(-EINVAL, "n_slots must be 1..%u", PK_BANK_MAX_SLOTS);
     HIPCHK(hipSetDevice(h->device));
     const size_t lists = (2 * (size_t)h->ngroups + 2 * (size_t)h->npad) * 4;
-    hipError_t e = hipMalloc((void**)&h->b_mem, (size_t)n_slots * PK_PHYS);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->b_regs, (size_t)n_slots * PK_BANK_REGS * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->b_lat, (size_t)n_slots * 3 * PK_ROWS * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->b_screen, (size_t)n_slots * PK_SCREEN);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->b_filled, n_slots);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->b_rejects, 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->b_lists, lists);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->b_src, (size_t)h->npad * 4);
-    if (e != hipSuccess) {
-        bank_free(h);
-        (void)hipGetLastError();
-        return fail(-ENOMEM, "bank of %u slots (%zu bytes each): %s", n_slots,
-                    (size_t)PK_PHYS + PK_BANK_REGS * 4 + 3 * PK_ROWS * 4 + PK_SCREEN, hipGetErrorString(e));
-    }
-    e = hipMemset(h->b_filled, 0, n_slots);
-    if (e == hipSuccess) e = hipMemset(h->b_rejects, 0, 4);
-    if (e == hipSuccess) e = hipMemset(h->b_lists, 0, lists);
-    if (e == hipSuccess) e = hipMemset(h->b_src, 0xFF, (size_t)h->npad * 4);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        bank_free(h);
+    Stage st(h);
+    st.want(h->b_mem, (size_t)n_slots * PK_PHYS);
+    st.want(h->b_regs, (size_t)n_slots * PK_BANK_REGS * 4);
+    st.want(h->b_lat, (size_t)n_slots * 3 * PK_ROWS * 4);
+    st.want(h->b_screen, (size_t)n_slots * PK_SCREEN);
+    st.want(h->b_filled, n_slots, 0);
+    st.want(h->b_rejects, 4, 0);
+    st.want(h->b_lists, lists, 0);
+    st.want(h->b_src, (size_t)h->npad * 4, 0xFF);
+    if (hipError_t e = st.run()) {
+        if (st.oom)
+            return fail(-ENOMEM, "bank of %u slots (%zu bytes each): %s", n_slots,
+                        (size_t)PK_PHYS + PK_BANK_REGS * 4 + 3 * PK_ROWS * 4 + PK_SCREEN, hipGetErrorString(e));
         return fail(-EIO, "bank setup failed: %s", hipGetErrorString(e));
     }
+    st.commit();
     h->bank_n = n_slots;
     return 0;
 }
@@ -1314,7 +1305,7 @@ uint32_t pk_bank_slots(const pk_handle* h) { return h ? h->bank_n : 0; }
 
 static int check_bank(pk_handle* h, uint32_t slot) {
     if (!h) return fail(-EINVAL, "null handle");
-    if (!h->bank_n) return fail(-ENOENT, "the handle has no bank (pk_bank_create)");
+    if (require_bank(h)) return -ENOENT;
     if (slot >= h->bank_n) return fail(-EINVAL, "slot %u out of range (%u slots)", slot, h->bank_n);
     return 0;
 }
@@ -1381,7 +1372,7 @@ static PkBankArgs bank_args(pk_handle* h, uint32_t mode, const int32_t* slots, u
 static int bank_move(pk_handle* h, uint32_t mode, const int32_t* slots, uint32_t env0, uint32_t count, void* stream) {
     int rc;
     if ((rc = check_range(h, env0, count))) return rc;
-    if (!h->bank_n) return fail(-ENOENT, "the handle has no bank (pk_bank_create)");
+    if (require_bank(h)) return -ENOENT;
     if (!slots) return fail(-EINVAL, "slot_of_env_dev is required");
     HIPCHK(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
@@ -1416,36 +1407,35 @@ static int bank_reset(pk_handle* h, const uint8_t* sel, const int32_t* slots, ui
     HIPCHK(hipMemsetAsync(b.cnt, 0, 8, s));
     HIPCHK(hipMemsetAsync(b.tcnt, 0, 4, s));
     HIPCHK(pk_launch_bank_list(b, s));
-    PkResetArgs a;
-    a.mem = h->mem; a.regs = h->regs; a.lat = h->lat; a.screen = h->screen;
-    a.tmpl_mem = h->t_mem; a.tmpl_regs = h->t_regs; a.tmpl_lat = h->t_lat; a.tmpl_screen = h->t_screen;
-    a.cnt = b.tcnt; a.ids = b.tids; a.n = h->n; a.npad = h->npad;
-    a.lat_stride = (uint32_t)h->lat_stride; a.env0 = env0; a.env1 = env1; a.ilv_sh = h->ilv_sh;
-    HIPCHK(pk_launch_reset(a, s));
+    HIPCHK(pk_launch_reset(reset_args(h, env0, env1), s));   // the range's reset list: b.tcnt, b.tids
     HIPCHK(pk_launch_bank_copy(b, s));
     return 0;
 }
 
-int pk_reset_from(pk_handle* h, uint32_t env0, uint32_t count, const uint8_t* mask, const int32_t* slots, void* stream) {
-    if (!slots) return pk_reset_range(h, env0, count, mask, stream);
+// The one reset of the masked envs of a range, behind pk_reset_range and pk_reset_from.  Without
+// slots the envs reload the template and their trajectories start at it; with slots they reload
+// through bank_reset, and the trajectory origin is the slot pk_bank_list_kernel validated (b_src:
+// -1 for the template, a rejected slot included).  With the reward stack the reload list is
+// rreset_pre's (the env's first reset only, or always with PK_F_RELOAD_ON_RESET), and the reset
+// ends with the observation of the masked envs.
+static int reset_envs(pk_handle* h, uint32_t env0, uint32_t count, const uint8_t* mask, const int32_t* slots, void* stream) {
     int rc;
     if ((rc = check_range(h, env0, count))) return rc;
-    if (!h->bank_n) return fail(-ENOENT, "the handle has no bank (pk_bank_create)");
-    const uint32_t env1 = env0 + count;
-    // the trajectory origin is the slot pk_bank_list_kernel validated (b_src: -1 for the template,
-    // a rejected slot included)
-    if (!(h->flags & PK_F_REWARD)) {
-        if ((rc = bank_reset(h, mask, slots, env0, env1, stream))) return rc;
-        return traj_reset(h, mask, nullptr, h->b_src, env0, env1, (hipStream_t)stream);
-    }
+    if (slots && require_bank(h)) return -ENOENT;
     HIPCHK(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
+    const uint32_t env1 = env0 + count;
+    const bool reward = (h->flags & PK_F_REWARD) != 0;
+    const uint8_t* reload = reward ? h->reload : nullptr;
     PkRewardArgs r = reward_args(h, env0, env1);
     r.env_mask = mask;
-    HIPCHK(pk_launch_rreset_pre(r, s));
-    if ((rc = bank_reset(h, h->reload, slots, env0, env1, stream))) return rc;
-    HIPCHK(pk_launch_rreset_post(r, s));
-    if ((rc = traj_reset(h, mask, h->reload, h->b_src, env0, env1, s))) return rc;
+    if (reward) HIPCHK(pk_launch_rreset_pre(r, s));
+    const uint8_t* sel = reward ? reload : mask;
+    if ((rc = slots ? bank_reset(h, sel, slots, env0, env1, stream) : template_reset(h, sel, env0, env1, stream))) return rc;
+    if (reward) HIPCHK(pk_launch_rreset_post(r, s));
+    if ((rc = traj_reset(h, mask, reload, slots ? h->b_src : nullptr, env0, env1, s))) return rc;
+    if (!reward) return 0;
+    // the observation of the reset envs only (list of the masked envs)
     HIPCHK(hipMemsetAsync(list_cnt(h, env0, 1), 0, 4, s));
     HIPCHK(pk_launch_list(mask, env0, env1, list_cnt(h, env0, 1), list_ids(h, env0, 1), s));
     r.ocnt = list_cnt(h, env0, 1);
@@ -1454,46 +1444,35 @@ int pk_reset_from(pk_handle* h, uint32_t env0, uint32_t count, const uint8_t* ma
     return 0;
 }
 
+int pk_reset_from(pk_handle* h, uint32_t env0, uint32_t count, const uint8_t* mask, const int32_t* slots, void* stream) {
+    return reset_envs(h, env0, count, mask, slots, stream);
+}
+
 // ---- episode checkpoints in the bank ----------------------------------------------------------
 
 int pk_bank_has_episodes(const pk_handle* h) { return (h && h->b_ep_filled) ? 1 : 0; }
 
 int pk_bank_enable_episodes(pk_handle* h) {
     if (!h) return fail(-EINVAL, "null handle");
-    if (!h->bank_n) return fail(-ENOENT, "the handle has no bank (pk_bank_create)");
+    if (require_bank(h)) return -ENOENT;
     if (!(h->flags & PK_F_REWARD)) return fail(-ENOTSUP, "episode checkpoints need the reward stack (PK_F_REWARD)");
     if (h->b_ep_filled) return fail(-EEXIST, "the bank already carries episode parts");
     static_assert(PK_NREGS <= PK_EP_RSD - PK_EP_REGS, "episode record layout");
     HIPCHK(hipSetDevice(h->device));
     const size_t K = h->bank_n, seen = K * (1ull << h->cap_log2) * 4;
-    uint32_t *f = nullptr, *sn = nullptr, *mk = nullptr, *cc = nullptr;
-    uint8_t* fl = nullptr;
-    // on a handle with trajectories the slots carry a trajectory part from the start
-    TrajBufs tb;
+    Stage st(h);
     int rc;
-    if (h->traj_cap && (rc = traj_alloc(K, h->traj_cap, std::vector<uint32_t>(K, 0u), tb))) return rc;
-    hipError_t e = hipMalloc((void**)&f, K * PK_EP_WORDS * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&sn, seen);
-    if (e == hipSuccess) e = hipMalloc((void**)&mk, K * PK_MASK_WORDS * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&cc, K * PK_CUTC_CAP * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&fl, K);
-    if (e == hipSuccess) e = hipMemset(f, 0, K * PK_EP_WORDS * 4);
-    if (e == hipSuccess) e = hipMemset(sn, 0, seen);
-    if (e == hipSuccess) e = hipMemset(mk, 0, K * PK_MASK_WORDS * 4);
-    if (e == hipSuccess) e = hipMemset(cc, 0, K * PK_CUTC_CAP * 4);
-    if (e == hipSuccess) e = hipMemset(fl, 0, K);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        void* ptrs[] = {f, sn, mk, cc, fl};
-        for (void* p : ptrs)
-            if (p) (void)hipFree(p);
-        traj_free(tb);
-        (void)hipGetLastError();
+    // on a handle with trajectories the slots carry a trajectory part from the start
+    if (h->traj_cap && (rc = traj_stage_slots(st, h, h->traj_cap, 0u))) return rc;
+    st.want(h->e_fields, K * PK_EP_WORDS * 4, 0);
+    st.want(h->e_seen, seen, 0);
+    st.want(h->e_mask, K * PK_MASK_WORDS * 4, 0);
+    st.want(h->e_cutc, K * PK_CUTC_CAP * 4, 0);
+    st.want(h->b_ep_filled, K, 0);
+    if (hipError_t e = st.run())
         return fail(-ENOMEM, "episode parts of %zu slots (%zu bytes each): %s", K,
                     (size_t)(seen / K) + (PK_MASK_WORDS + PK_CUTC_CAP + PK_EP_WORDS) * 4 + 1, hipGetErrorString(e));
-    }
-    h->e_fields = f; h->e_seen = sn; h->e_mask = mk; h->e_cutc = cc; h->b_ep_filled = fl;
-    h->bt_act = tb.act; h->bt_origin = tb.origin; h->bt_flags = tb.flags;
+    st.commit();
     return 0;
 }
 
@@ -1515,7 +1494,7 @@ int pk_bank_enable_generic_episodes(pk_handle* h, uint32_t parts) {
     if (!h) return fail(-EINVAL, "null handle");
     if (h->flags & PK_F_REWARD)
         return fail(-ENOTSUP, "generic episode parts are for handles without the reward stack (pk_bank_enable_episodes)");
-    if (!h->bank_n) return fail(-ENOENT, "the handle has no bank (pk_bank_create)");
+    if (require_bank(h)) return -ENOENT;
     if (parts & ~(PK_GEP_PROBES | PK_GEP_STACK)) return fail(-EINVAL, "unknown parts 0x%x", parts);
     if ((parts & PK_GEP_PROBES) && !h->pr_m) return fail(-ENOENT, "PK_GEP_PROBES: the handle has no probe program (pk_probe_create)");
     if ((parts & PK_GEP_STACK) && !h->fs_depth) return fail(-ENOENT, "PK_GEP_STACK: the handle has no frame stack (pk_fstack_create)");
@@ -1524,33 +1503,19 @@ int pk_bank_enable_generic_episodes(pk_handle* h, uint32_t parts) {
                   PK_SCREEN % 256u == 0u, "generic episode part layout");
     HIPCHK(hipSetDevice(h->device));
     const size_t K = h->bank_n, rb = K * PK_GEP_REGS * 4, pb = K * gep_mpad(h, parts) * 4, sb = K * gep_row(h, parts);
-    uint32_t *gr = nullptr, *gp = nullptr;
-    uint8_t *gs = nullptr, *fl = nullptr;
-    // on a handle with trajectories the slots carry a trajectory part from the start
-    TrajBufs tb;
+    Stage st(h);
     int rc;
-    if (h->traj_cap && (rc = traj_alloc(K, h->traj_cap, std::vector<uint32_t>(K, 0u), tb))) return rc;
-    hipError_t e = hipMalloc((void**)&gr, rb);
-    if (e == hipSuccess && pb) e = hipMalloc((void**)&gp, pb);
-    if (e == hipSuccess && sb) e = hipMalloc((void**)&gs, sb);
-    if (e == hipSuccess) e = hipMalloc((void**)&fl, K);
-    if (e == hipSuccess) e = hipMemset(gr, 0, rb);
-    if (e == hipSuccess && pb) e = hipMemset(gp, 0, pb);
-    if (e == hipSuccess && sb) e = hipMemset(gs, 0, sb);
-    if (e == hipSuccess) e = hipMemset(fl, 0, K);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        void* ptrs[] = {gr, gp, gs, fl};
-        for (void* p : ptrs)
-            if (p) (void)hipFree(p);
-        traj_free(tb);
-        (void)hipGetLastError();
+    // on a handle with trajectories the slots carry a trajectory part from the start
+    if (h->traj_cap && (rc = traj_stage_slots(st, h, h->traj_cap, 0u))) return rc;
+    st.want(h->g_regs, rb, 0);
+    st.want(h->g_probe, pb, 0);
+    st.want(h->g_stack, sb, 0);
+    st.want(h->b_ep_filled, K, 0);
+    if (hipError_t e = st.run())
         return fail(-ENOMEM, "generic episode parts of %zu slots (%zu bytes each): %s", K, (rb + pb + sb) / K + 1,
                     hipGetErrorString(e));
-    }
-    h->g_regs = gr; h->g_probe = gp; h->g_stack = gs; h->b_ep_filled = fl;
+    st.commit();
     h->gep_parts = parts | 0x80000000u;
-    h->bt_act = tb.act; h->bt_origin = tb.origin; h->bt_flags = tb.flags;
     return 0;
 }
 
@@ -1559,7 +1524,7 @@ int pk_bank_enable_generic_episodes(pk_handle* h, uint32_t parts) {
 static int episode_move(pk_handle* h, uint32_t mode, const int32_t* slots, uint32_t env0, uint32_t count, void* stream) {
     int rc;
     if ((rc = check_range(h, env0, count))) return rc;
-    if (!h->bank_n) return fail(-ENOENT, "the handle has no bank (pk_bank_create)");
+    if (require_bank(h)) return -ENOENT;
     if (!h->b_ep_filled) return fail(-ENOENT, "the bank carries no episode parts (pk_bank_enable_episodes)");
     if (!slots) return fail(-EINVAL, "slot_of_env_dev is required");
     HIPCHK(hipSetDevice(h->device));
@@ -1569,9 +1534,9 @@ static int episode_move(pk_handle* h, uint32_t mode, const int32_t* slots, uint3
     HIPCHK(hipMemsetAsync(a.cnt, 0, 8, s));
     HIPCHK(pk_launch_bank_list(a, s));
     HIPCHK(pk_launch_bank_copy(a, s));
+    const uint32_t save = mode == PK_BANK_SAVE ? 1u : 0u;
     if (h->gep_parts) {
-        // no reward stack: the generic mover over the same list, then the trajectory part; there is
-        // no reward observation to rebuild
+        // no reward stack: the generic mover over the same list
         PkGepArgs g;
         memset(&g, 0, sizeof g);
         g.regs = h->regs; g.g_regs = h->g_regs;
@@ -1579,32 +1544,27 @@ static int episode_move(pk_handle* h, uint32_t mode, const int32_t* slots, uint3
         if (h->gep_parts & PK_GEP_STACK) { g.stack = h->fs_stack; g.g_stack = h->g_stack; }
         g.mpad = gep_mpad(h, h->gep_parts); g.row16 = gep_row(h, h->gep_parts) / 16u;
         g.cnt = a.cnt; g.ids = a.ids; g.src = a.src;
-        g.npad = h->npad; g.save = mode == PK_BANK_SAVE ? 1u : 0u; g.items = count;
+        g.npad = h->npad; g.save = save; g.items = count;
         HIPCHK(pk_launch_gep_move(g, s));
-        if (h->traj_cap) {
-            PkTrajArgs t = traj_args(h, env0, env0 + count);
-            t.cnt = a.cnt; t.ids = a.ids; t.src = a.src;
-            t.save = g.save; t.items = count;
-            HIPCHK(pk_launch_traj_move(t, s));
-        }
-        return 0;
+    } else {
+        PkEpArgs p;
+        memset(&p, 0, sizeof p);
+        p.regs = h->regs; p.rs = h->rs; p.rsd = h->rsd; p.seen = h->seen; p.mask = h->mask; p.cutc = h->cutc;
+        p.e_fields = h->e_fields; p.e_seen = h->e_seen; p.e_mask = h->e_mask; p.e_cutc = h->e_cutc;
+        p.cnt = a.cnt; p.ids = a.ids; p.src = a.src;
+        p.npad = h->npad; p.nregs = PK_NREGS; p.cap_log2 = h->cap_log2; p.save = save;
+        p.items = count;
+        HIPCHK(pk_launch_ep_move(p, s));
     }
-    PkEpArgs p;
-    memset(&p, 0, sizeof p);
-    p.regs = h->regs; p.rs = h->rs; p.rsd = h->rsd; p.seen = h->seen; p.mask = h->mask; p.cutc = h->cutc;
-    p.e_fields = h->e_fields; p.e_seen = h->e_seen; p.e_mask = h->e_mask; p.e_cutc = h->e_cutc;
-    p.cnt = a.cnt; p.ids = a.ids; p.src = a.src;
-    p.npad = h->npad; p.nregs = PK_NREGS; p.cap_log2 = h->cap_log2; p.save = mode == PK_BANK_SAVE ? 1u : 0u;
-    p.items = count;
-    HIPCHK(pk_launch_ep_move(p, s));
     if (h->traj_cap) {
         // the trajectory part over the same list; a resumed env's step counter is the slot's by now
         PkTrajArgs t = traj_args(h, env0, env0 + count);
         t.cnt = a.cnt; t.ids = a.ids; t.src = a.src;
-        t.save = p.save; t.items = count;
+        t.save = save; t.items = count;
         HIPCHK(pk_launch_traj_move(t, s));
     }
-    if (mode == PK_BANK_LOAD) {
+    // with the reward stack a resume rebuilds the observation of the listed envs
+    if (!h->gep_parts && mode == PK_BANK_LOAD) {
         PkRewardArgs r = reward_args(h, env0, env0 + count);
         r.ocnt = a.cnt;
         r.oids = a.ids;
@@ -1623,7 +1583,7 @@ int pk_bank_resume(pk_handle* h, const int32_t* slots, uint32_t env0, uint32_t c
 
 int pk_bank_rejects(pk_handle* h, uint64_t* out) {
     if (!h || !out) return fail(-EINVAL, "null argument");
-    if (!h->bank_n) return fail(-ENOENT, "the handle has no bank (pk_bank_create)");
+    if (require_bank(h)) return -ENOENT;
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipDeviceSynchronize());
     uint32_t v = 0;
@@ -1706,23 +1666,16 @@ int pk_archive_create(pk_handle* h, uint32_t slot0, uint32_t n_cells, uint64_t s
     const uint32_t I = pow2_at_least(2ull * n_cells), S = pow2_at_least(2ull * h->npad);
     const size_t fix = arch_fix_bytes(n_cells, I, h->npad);
     const size_t ones = ((size_t)n_cells + 2ull * S) * 8 + (size_t)S * 4, zero = ((size_t)n_cells + S) * 8 + 2ull * S * 4;
-    uint8_t *pf = nullptr, *po = nullptr, *pz = nullptr;
-    hipError_t e = hipMalloc((void**)&pf, fix);
-    if (e == hipSuccess) e = hipMalloc((void**)&po, ones);
-    if (e == hipSuccess) e = hipMalloc((void**)&pz, zero);
-    if (e == hipSuccess) e = hipMemset(pf, 0, fix);
+    Stage st(h);
+    st.want(h->a_fix, fix, 0);
     // no cell has a key yet, the index is empty
-    if (e == hipSuccess) e = hipMemset(pf + PK_AH_WORDS * 8, 0xFF, (size_t)n_cells * 8);
-    if (e == hipSuccess) e = hipMemset(pf + ((size_t)PK_AH_WORDS + 3ull * n_cells) * 8, 0xFF, (size_t)I * 8);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        void* ptrs[] = {pf, po, pz};
-        for (void* p : ptrs)
-            if (p) (void)hipFree(p);
-        (void)hipGetLastError();
+    st.fill(h->a_fix, PK_AH_WORDS * 8, (size_t)n_cells * 8, 0xFF);
+    st.fill(h->a_fix, ((size_t)PK_AH_WORDS + 3ull * n_cells) * 8, (size_t)I * 8, 0xFF);
+    st.want(h->a_ones, ones);
+    st.want(h->a_zero, zero);
+    if (hipError_t e = st.run())
         return fail(-ENOMEM, "archive of %u cells (%zu bytes): %s", n_cells, fix + ones + zero, hipGetErrorString(e));
-    }
-    h->a_fix = pf; h->a_ones = po; h->a_zero = pz;
+    st.commit();
     h->arch_cells = n_cells; h->arch_slot0 = slot0; h->arch_imask = I - 1u; h->arch_seed = seed;
     return 0;
 }
@@ -1777,16 +1730,11 @@ int pk_fstack_create(pk_handle* h, uint32_t scale, uint32_t depth, uint32_t layo
     if (layout == PK_FSTACK_HWC && (depth & (depth - 1u))) return fail(-EINVAL, "depth must be 1, 2, 4 or 8 with PK_FSTACK_HWC");
     HIPCHK(hipSetDevice(h->device));
     const size_t bytes = (size_t)h->n * depth * (PK_SCREEN / (scale * scale));
-    uint8_t* p = nullptr;
-    hipError_t e = hipMalloc((void**)&p, bytes);
-    if (e == hipSuccess) e = hipMemset(p, 0, bytes);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        if (p) (void)hipFree(p);
-        (void)hipGetLastError();
+    Stage st(h);
+    st.want(h->fs_stack, bytes, 0);
+    if (hipError_t e = st.run())
         return fail(-ENOMEM, "frame stack of depth %u at scale %u (%zu bytes): %s", depth, scale, bytes, hipGetErrorString(e));
-    }
-    h->fs_stack = p;
+    st.commit();
     h->fs_scale = scale; h->fs_depth = depth; h->fs_layout = layout; h->fs_mode = mode;
     return 0;
 }
@@ -1839,20 +1787,13 @@ int pk_probe_create(pk_handle* h, const pk_probe* prog, uint32_t m) {
     }
     HIPCHK(hipSetDevice(h->device));
     const size_t pbytes = (size_t)m * sizeof(pk_probe), sbytes = (size_t)m * h->npad * 4;
-    pk_probe* dp = nullptr;
-    uint32_t* ds = nullptr;
-    hipError_t e = hipMalloc((void**)&dp, pbytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&ds, sbytes);
-    if (e == hipSuccess) e = hipMemcpy(dp, prog, pbytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(ds, 0, sbytes);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        if (dp) (void)hipFree(dp);
-        if (ds) (void)hipFree(ds);
-        (void)hipGetLastError();
+    Stage st(h);
+    st.want(h->pr_prog, pbytes, -1, prog);
+    st.want(h->pr_state, sbytes, 0);
+    if (hipError_t e = st.run())
         return fail(-ENOMEM, "probe program of %u probes (%zu bytes of state): %s", m, sbytes, hipGetErrorString(e));
-    }
-    h->pr_prog = dp; h->pr_state = ds; h->pr_m = m;
+    st.commit();
+    h->pr_m = m;
     return 0;
 }
 
@@ -2022,21 +1963,13 @@ int pk_archive_exchange_enable(pk_handle* h) {
     HIPCHK(hipSetDevice(h->device));
     const uint32_t K = h->arch_cells, R = PK_XCHG_MAX_RECORDS, S = pow2_at_least(2ull * R);
     const size_t fix = (3ull * K + 3ull * R) * 4 + R, ones = xchg_ones_bytes(K, S), zero = xchg_zero_bytes(K, S) + (size_t)S * 4;
-    uint8_t *pf = nullptr, *po = nullptr, *pz = nullptr;
-    hipError_t e = hipMalloc((void**)&pf, fix);
-    if (e == hipSuccess) e = hipMalloc((void**)&po, ones);
-    if (e == hipSuccess) e = hipMalloc((void**)&pz, zero);
-    if (e == hipSuccess) e = hipMemset(pf, 0, fix);
-    if (e == hipSuccess) e = hipMemset(pz, 0, zero);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        void* ptrs[] = {pf, po, pz};
-        for (void* p : ptrs)
-            if (p) (void)hipFree(p);
-        (void)hipGetLastError();
+    Stage st(h);
+    st.want(h->x_fix, fix, 0);
+    st.want(h->x_ones, ones);
+    st.want(h->x_zero, zero, 0);
+    if (hipError_t e = st.run())
         return fail(-ENOMEM, "exchange words of %u cells (%zu bytes): %s", K, fix + ones + zero, hipGetErrorString(e));
-    }
-    h->x_fix = pf; h->x_ones = po; h->x_zero = pz;
+    st.commit();
     return 0;
 }
 
@@ -2117,16 +2050,12 @@ int pk_traj_enable(pk_handle* h) {
     std::vector<uint32_t> flags(h->npad, 0u);
     HIPCHK(hipMemcpy(flags.data(), h->regs + (size_t)PK_R_TIME * h->npad, (size_t)h->npad * 4, hipMemcpyDeviceToHost));
     for (uint32_t& f : flags) f = f ? PK_TRAJ_BROKEN : 0u;
-    TrajBufs envs, slots;
+    Stage st(h);
     int rc;
-    if ((rc = traj_alloc(h->npad, cap, flags, envs))) return rc;
+    if ((rc = traj_stage_envs(st, h, cap, flags))) return rc;
     // slots that already hold an episode hold no actions for it
-    if (h->b_ep_filled && (rc = traj_alloc(h->bank_n, cap, std::vector<uint32_t>(h->bank_n, PK_TRAJ_BROKEN), slots))) {
-        traj_free(envs);
-        return rc;
-    }
-    h->t_act = envs.act; h->t_origin = envs.origin; h->t_flags = envs.flags;
-    h->bt_act = slots.act; h->bt_origin = slots.origin; h->bt_flags = slots.flags;
+    if (h->b_ep_filled && (rc = traj_stage_slots(st, h, cap, PK_TRAJ_BROKEN))) return rc;
+    st.commit();
     h->cap_log2 = lg;
     h->traj_cap = cap;
     return 0;
@@ -2155,7 +2084,7 @@ int pk_bank_traj_get(pk_handle* h, uint32_t slot0, uint32_t count, int32_t* orig
                      uint8_t* actions, void* stream) {
     if (!h) return fail(-EINVAL, "null handle");
     if (!h->traj_cap) return fail(-ENOENT, "the handle records no trajectories (pk_traj_enable)");
-    if (!h->bank_n) return fail(-ENOENT, "the handle has no bank (pk_bank_create)");
+    if (require_bank(h)) return -ENOENT;
     if (count == 0 || (uint64_t)slot0 + count > h->bank_n)
         return fail(-EINVAL, "slots [%u, +%u) are not inside the bank's %u", slot0, count, h->bank_n);
     return traj_get(h, true, slot0, count, origin, len, flags, actions, stream);
@@ -2165,23 +2094,23 @@ int pk_bank_traj_get(pk_handle* h, uint32_t slot0, uint32_t count, int32_t* orig
 
 static uint64_t counts_limit(uint32_t lg) { return 3ull << (lg - 2u); }
 
-// c_fix: header | keys | counts | sent | per-env entry words
-static PkCountArgs counts_args(const pk_handle* h) {
+// a table of 2^lg entries in the block c_fix: header | keys | counts | sent | per-env entry words
+static PkCountArgs counts_layout(uint8_t* c_fix, uint32_t lg) {
     PkCountArgs a;
     memset(&a, 0, sizeof a);
-    const size_t cap = (size_t)1 << h->cnt_log2;
-    a.hdr = (uint64_t*)h->c_fix;
+    const size_t cap = (size_t)1 << lg;
+    a.hdr = (uint64_t*)c_fix;
     a.c_key = a.hdr + PK_CH_WORDS;
     a.c_cnt = a.c_key + cap;
     a.c_sent = a.c_cnt + cap;
     a.tgt = (uint32_t*)(a.c_sent + cap);
     a.c_mask = (uint32_t)(cap - 1u);
-    a.limit = counts_limit(h->cnt_log2);
+    a.limit = counts_limit(lg);
     return a;
 }
+static PkCountArgs counts_args(const pk_handle* h) { return counts_layout(h->c_fix, h->cnt_log2); }
 
-static hipError_t counts_wipe(const pk_handle* h, hipStream_t s) {
-    const PkCountArgs a = counts_args(h);
+static hipError_t counts_wipe(const PkCountArgs& a, hipStream_t s) {
     const size_t cap = (size_t)a.c_mask + 1u;
     hipError_t e = hipMemsetAsync(a.hdr, 0, PK_CH_WORDS * 8, s);
     if (e == hipSuccess) e = hipMemsetAsync(a.c_key, 0xFF, cap * 8, s);
@@ -2201,21 +2130,17 @@ int pk_counts_create(pk_handle* h, uint32_t cap_log2) {
                     (unsigned long long)counts_limit(cap_log2), h->n);
     HIPCHK(hipSetDevice(h->device));
     const size_t bytes = PK_CH_WORDS * 8 + ((size_t)24 << cap_log2) + (size_t)h->npad * 4;
-    uint8_t* p = nullptr;
-    hipError_t e = hipMalloc((void**)&p, bytes);
-    if (e == hipSuccess) {
-        h->c_fix = p;
-        h->cnt_log2 = cap_log2;
-        e = counts_wipe(h, nullptr);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-    }
+    Stage st(h);
+    st.want(h->c_fix, bytes);
+    hipError_t e = st.run();
+    if (e == hipSuccess) e = counts_wipe(counts_layout(st.staged(h->c_fix), cap_log2), nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
-        if (p) (void)hipFree(p);
-        h->c_fix = nullptr;
-        h->cnt_log2 = 0;
         (void)hipGetLastError();
         return fail(-ENOMEM, "count table of 2^%u entries (%zu bytes): %s", cap_log2, bytes, hipGetErrorString(e));
     }
+    st.commit();
+    h->cnt_log2 = cap_log2;
     return 0;
 }
 
@@ -2281,7 +2206,7 @@ int pk_counts_clear(pk_handle* h, void* stream) {
     if (!h) return fail(-EINVAL, "null handle");
     if (!h->cnt_log2) return fail(-ENOENT, "the handle has no count table (pk_counts_create)");
     HIPCHK(hipSetDevice(h->device));
-    HIPCHK(counts_wipe(h, (hipStream_t)stream));
+    HIPCHK(counts_wipe(counts_args(h), (hipStream_t)stream));
     return 0;
 }
 

@@ -110,15 +110,16 @@ static inline hipError_t hipSetDevice(int) { return hipSuccess; }
 static inline hipError_t hipDeviceSynchronize() { return hipSuccess; }
 enum hipDeviceAttribute_t { hipDeviceAttributeMultiprocessorCount = 1 };
 static inline hipError_t hipDeviceGetAttribute(int* v, hipDeviceAttribute_t, int) { *v = 256; return hipSuccess; }
-static inline hipError_t hipMalloc(void** p, size_t n) {
-    *p = aligned_alloc(256, (n + 255) / 256 * 256);
-    return *p ? hipSuccess : hipErrorOutOfMemory;
-}
-static inline hipError_t hipFree(void* p) { free(p); return hipSuccess; }
+// allocations are counted, and one can be made to fail (hostsim_rt.cpp: pk_sim_alloc_live,
+// pk_sim_alloc_fail_at)
+hipError_t hipMalloc(void** p, size_t n);
+hipError_t hipFree(void* p);
 static inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { memmove(d, s, n); return hipSuccess; }
 static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { memmove(d, s, n); return hipSuccess; }
 static inline hipError_t hipMemset(void* d, int v, size_t n) { memset(d, v, n); return hipSuccess; }
-static inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { memset(d, v, n); return hipSuccess; }
+// recorded beside the launches while pk_sim_record_enable is on (hostsim_rt.cpp)
+void pk_sim_record_memset(size_t n);
+static inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { pk_sim_record_memset(n); memset(d, v, n); return hipSuccess; }
 static inline uint32_t atomicAdd(uint32_t* p, uint32_t v) { return __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
 static inline hipError_t hipEventCreate(hipEvent_t* e) { *e = nullptr; return hipSuccess; }
 static inline hipError_t hipEventDestroy(hipEvent_t) { return hipSuccess; }

@@ -31,9 +31,62 @@ static void launch_independent(dim3 grid, dim3 block, const std::function<void()
     for (auto& th : ts) th.join();
 }
 
+// ---- allocation accounting: live allocations, and a hipMalloc made to fail ----
+static std::atomic<int64_t> g_alloc_live{0}, g_alloc_calls{0}, g_alloc_fail{-1};
+hipError_t hipMalloc(void** p, size_t n) {
+    *p = nullptr;
+    g_alloc_calls++;
+    // the k-th hipMalloc after pk_sim_alloc_fail_at(k) fails (k = 0: the next one), once
+    if (g_alloc_fail.load() >= 0 && g_alloc_fail.fetch_sub(1) == 0) return hipErrorOutOfMemory;
+    *p = aligned_alloc(256, (n + 255) / 256 * 256);
+    if (!*p) return hipErrorOutOfMemory;
+    g_alloc_live++;
+    return hipSuccess;
+}
+hipError_t hipFree(void* p) {
+    if (p) g_alloc_live--;
+    free(p);
+    return hipSuccess;
+}
+extern "C" int64_t pk_sim_alloc_live(void) { return g_alloc_live.load(); }
+extern "C" int64_t pk_sim_alloc_calls(void) { return g_alloc_calls.load(); }   // every hipMalloc so far
+extern "C" void pk_sim_alloc_fail_at(int64_t k) { g_alloc_fail.store(k < 0 ? -1 : k); }
+
+// ---- launch sequence: "L <kernel> <grid.x> <block.x>" per launch, "M <bytes>" per hipMemsetAsync ----
+static std::mutex g_rec_mu;
+static std::string g_rec;
+static bool g_rec_on = false;
+extern "C" void pk_sim_record_enable(int on) {
+    std::lock_guard<std::mutex> l(g_rec_mu);
+    g_rec.clear();
+    g_rec_on = on != 0;
+}
+// the text so far (cleared); returns its length, which may exceed cap
+extern "C" uint64_t pk_sim_record_get(char* out, uint64_t cap) {
+    std::lock_guard<std::mutex> l(g_rec_mu);
+    const uint64_t n = g_rec.size();
+    if (out && cap) {
+        const uint64_t m = n < cap - 1 ? n : cap - 1;
+        memcpy(out, g_rec.data(), m);
+        out[m] = 0;
+    }
+    g_rec.clear();
+    return n;
+}
+void pk_sim_record_memset(size_t n) {
+    std::lock_guard<std::mutex> l(g_rec_mu);
+    if (g_rec_on) g_rec += "M " + std::to_string(n) + "\n";
+}
+
 void pk_sim_launch(const char* name, dim3 grid, dim3 block, const std::function<void()>& body) {
     // the only kernel with __shared__ + __syncthreads (pk_step.hip launches it as PK_K1_KERNEL)
     while (*name == '(') name++;
+    {
+        std::lock_guard<std::mutex> l(g_rec_mu);
+        if (g_rec_on)
+            g_rec += "L " + std::string(name, strcspn(name, ")")) + " " + std::to_string(grid.x) + " " +
+                     std::to_string(block.x) + "\n";
+    }
     if (strncmp(name, "pk_step_kernel", 14) != 0 && strncmp(name, "PK_K1_KERNEL", 12) != 0) {
         launch_independent(grid, block, body);
         return;
