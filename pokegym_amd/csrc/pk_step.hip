@@ -805,29 +805,32 @@ __device__ __forceinline__ void pk_exec(St& s, const Ctx& c, u32 pc, u32 bytes, 
     // each bit.  Left rotates and shifts are X + X + (0 / F.C / bit 7): bit 8 is the carry out
     r = X + (Y ^ m.YX) + cin;
     cvx = X ^ Y ^ r;
-    // right-shift unit: RRC RRA RR SRA SRL ((X | in << 8 | X.0 << 9) >> 1: bit 8 = the bit
-    // shifted out) and SWAP ((X | X << 8) >> 4)
-    {
-        const u32 swap = bmask(U, PK_US_SWAP);
-        rs = (X | (msel(swap, X, cin | ((X & 1u) << 1)) << 8)) >> msel(swap, 4u, 1u);
-    }
+    // right-shift unit: RRC RRA RR SRA SRL (X >> 1 | in << 7 | X << 8: bit 8 = the bit shifted out)
+    // and SWAP (X >> 4 | X << 4) as one multiply-add and one shift, the multiplier in CI's spare
+    // bits and the shift in U's low five (pk_ucode.h PK_US_RSH); bits above 8 are garbage no
+    // consumer takes
+    rs = ((X & 0xFFFFFFu) * (m.CI & 0xFFFFFFu) + (cin << PK_RS_IN)) >> (U & 31u);
     // logic: (X & Y) and/or (X ^ Y) (OR = both); loads are 0xFF AND Y
     lres = ((X & Y) & (u32)sfield(U, PK_US_LAND, 1)) | ((X ^ Y) & (u32)sfield(U, PK_US_LXOR, 1));
     const u32 res8 = msel(bmask(U, PK_US_LOGIC), lres, msel(right, rs, r)) & 0xFFu;
-    // flags: F' = (F & FK) | ((Z | H | C | FC) & FM), H/C = carry bits 4/8 (12/16 for ADD HL) or
-    // the right unit's shifted-out bit 8
+    // flags: F' = ((Z | H | C) & CM) | FC | (F & FK) | (Y & FY) (pk_ucode.h K word; Y & FY: POP AF
+    // and DAA load m0 & 0xF0), H/C = carry bits 4/8 (12/16 for ADD HL: CI's low bits are that
+    // shift) or the right unit's shifted-out bit 8.  The masks lie in the flag nibble and CM sits in
+    // place with K's low nibble clear, so the two carries are masked once and shifted into place
+    // together, and only F's byte of nf is defined: bits above it are garbage, and the writeback
+    // takes nf's low byte alone.
     u32 nf = F;
     {
-        const u32 cs = msel(right, rs, cvx) >> (U & (1u << PK_US_HSH8));   // >> 8 for ADD HL
-        const u32 fv = sel(res8 == 0u, 0x80u, 0u) | ((cs << 1) & 0x20u) | ((cs >> 4) & 0x10u) | K;
-        nf = ((F & (K >> 8)) | (fv & (K >> 16))) & 0xFFu;
-        nf = msel(bmask(U, PK_US_FPOP), m16 & 0xF0u, nf);
+        const u32 cs = (msel(right, rs, cvx) >> (m.CI & 31u)) & 0x110u;
+        const u32 hc = (cs >> 4) | (cs << 1);   // C, H (and bits 0 and 9, which no mask takes)
+        const u32 fv = ((hc | sel(res8 == 0u, 0x80u, 0u)) & K) | ((K >> 8) & 0xFFu);
+        nf = fv | ((w1 >> 16) & (K >> 16)) | (Y & (U >> 16));
     }
     // register writeback: val = res16 | F' << 16 | res8 << 24 through the per-op byte selectors
     // (res16: the adder, or HL +- 1 for (HL+)/(HL-); bytes 2-3 of either are not taken)
     const u32 u16 = msel(bmask(U, PK_US_R16HL), w1 + (u32)sfield(U, PK_US_HLINC, 2), r);
     {
-        const u32 val = perm(nf | (res8 << 8), u16, 0x05040100u);
+        const u32 val = perm(perm(res8, nf, 0x0C0C0400u), u16, 0x05040100u);
         s.w0 = perm(val, w0, m.S0);
         s.w1 = perm(val, w1, m.S1);
     }
@@ -1284,19 +1287,21 @@ __global__ void __launch_bounds__(PK_K1_MAX_THREADS) PK_K1_KERNEL(PkStepArgs A) 
             const u32 cin = (bit(F1, 4) & ctl) ^ bit(ctl, PK_U2C_SUBC);
             const u32 r = x + yy + cin;
             const u32 cvec = x ^ yy ^ r;
-            const u32 hc = ((cvec << 1) & 0x20u) | ((cvec >> 4) & 0x10u);   // H: carry into bit 4, C: into bit 8
+            // the flag unit, in place at F's byte of w1 (pk_ucode.h PK_U2_FPOS): H = the carry into bit
+            // 4, C = into bit 8, shifted to bits 21 and 20 (the shifts' other two bits fall on bit
+            // 16, which MASK clears, and outside F's byte); only F's byte of Fn is defined
+            const u32 hc = ((cvec & 0x110u) << 12) | ((cvec & 0x110u) << 17);
             const u32 lr = (x & yv & (0u - bit(ctl, PK_U2C_LA))) | ((x ^ yv) & (0u - bit(ctl, PK_U2C_LX)));
-            const u32 res = sel(ctl & (1u << PK_U2C_LOGIC), lr, r);
-            const u32 comp = sel((res & 0xFFu) == 0u, 0x80u, 0u) | ((hc ^ (ctl >> PK_U2C_FLIP)) & (ctl >> PK_U2C_HCM))
-                           | (ctl >> PK_U2C_FCONST);
-            const u32 fm = M2 >> PK_U2B_FM;
-            const u32 Fn = (comp & fm) | (F1 & ~fm);
-            const u32 val2 = perm(Fn, res, 0x00040100u);
+            const u32 res = msel(bmask(ctl, PK_U2C_LOGIC), lr, r);
+            const u32 kept = s.w1 & u2.x;   // F & FK (JR: F & the condition's mask)
+            const u32 Fn = (((hc ^ u2b.z) | sel((res & 0xFFu) == 0u, 0x80u << PK_U2_FPOS, 0u)) & ctl) | u2b.y | kept;
+            const u32 val2 = perm(Fn, res, 0x00060100u);
+            // (an entry that writes no flag, and the not-fused case, take F from w1: PK_S1_KEEP)
             const u32 w0f = perm(val2, s.w0, sel(fuse, u2.z, PK_S0_ID));
-            const u32 w1f = perm(val2, s.w1, sel(fuse, u2.w, PK_S1_ID));
+            const u32 w1f = perm(val2, s.w1, sel(fuse, u2.w, PK_S1_KEEP));
             // JR: taken when (F & mask) == cv (mask at F's byte of the x word, cv at the same byte of
             // the misc word; never for the other entries and when not fused)
-            const bool tk2 = (((s.w1 & u2.x) ^ M2) & 0x00FF0000u) == 0u;
+            const bool tk2 = ((kept ^ M2) & 0x00FF0000u) == 0u;
             const u32 pc2 = (s.pc + (M2 & 3u) + sel(tk2, (u32)sfield(nxt, 8, 8), 0u)) & 0xFFFFu;
             if (fuse) PK_TRACE(env, s.pc, s.w0, perm(s.w1, s.w1, 0x02030100u), s.sp, (nxt & 0xFFu) | 0x2000u);
             ev |= sel(fuse, PK_EV_FUSE, 0u);

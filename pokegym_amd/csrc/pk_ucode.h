@@ -22,7 +22,11 @@
 enum { PK_UE_D = 0, PK_UE_U, PK_UE_K, PK_UE_V, PK_UE_XR, PK_UE_XE, PK_UE_YR, PK_UE_YE, PK_UE_AR, PK_UE_AE,
        PK_UE_S0, PK_UE_S1, PK_UE_YC, PK_UE_YX, PK_UE_CW, PK_UE_CI, PK_UE_WORDS };
 // stored words (what the kernel reads; the builder below works in the PK_UB_/PK_KB_ form):
-//   U  datapath control bits PK_US_*          K  FC | FK << 8 | FM << 16 | CPUAND << 24 | CPUOR << 28
+//   U  datapath control bits PK_US_*          K  CM | FC << 8 | FK << 16 | CPUAND << 24 | CPUOR << 28
+//      flags: F' = ((Z | H | C) & CM) | FC | (F & FK) | (Y & FY): CM the computed flags the op takes, FC
+//      the flags it sets, FK the flags it keeps, FY (U word) the bits of Y's low byte it loads (POP AF,
+//      DAA: 0xF0); the four masks are disjoint and lie in the flag nibble, a flag in none is cleared.
+//      CM sits in place (K bits 4-7, bits 0-3 clear: the kernel ANDs the computed flags with K itself)
 //   V  the successor selector: bytes 0-1 = a v_perm selector taking the fetched bytes' successor
 //      opcode and operand (bytes len, len + 1), or 0xFF (0x0D: RST 38h, no secondary op) for a
 //      primary that may not fuse; | cycles << 16 | extra cycles when the condition holds << 24 (the D
@@ -31,21 +35,31 @@ enum { PK_UE_D = 0, PK_UE_U, PK_UE_K, PK_UE_V, PK_UE_XR, PK_UE_XE, PK_UE_YR, PK_
 //      pc + len + Y; Y's bits above 16 reach no result)                YX 0x1FFFF when the adder subtracts
 //   CW/CI carry-in (adder) / shifted-in bit (right-shift unit) = bit CW of (X | F << 16) ^ CI:
 //         bit 20 = F.C, bit 7/bit 0 = X's top/bottom bit, bit 16 = constant 0 (with CI: constant 1)
-#define PK_US_LOGIC 0     // result8 from the logic unit (loads: X = 0xFF AND Y), else adder / right unit
-#define PK_US_RIGHT 1     // result8 and C from the right-shift unit
-#define PK_US_SWAP 2      // right-shift unit: nibble swap
-#define PK_US_HSH8 3      // H/C from carry bits 12/16 (ADD HL,rr), else 4/8 (at bit 3: U & 8 is the shift)
-#define PK_US_JUMP 4      // control transfer to X + Y (+ pc + len for JR) when the condition holds
+//      CW is one bit (or 0), so CI's other bits are free and carry two more fields the kernel takes
+//      from the word in place: bits 0-4 the shift that brings the H/C carries down (8 for ADD HL,rr:
+//      carries 12/16, else 0), and for the right-shift unit its multiplier PK_CI_RMUL / PK_CI_SMUL
+//      (bits 5-14), see PK_US_RSH.  None of them may meet CW's bit (tests/test_ucode_flags.py)
+// right-shift unit: rs = (X * mul + in << 13) >> RSH, one multiply-add and one shift for both forms:
+//   RRC RRA RR SRA SRL  mul = 1 << 5 | 1 << 14, RSH 6:  X >> 1 | in << 7 | X << 8 (bit 8 = the bit shifted out)
+//   SWAP                mul = 1 << 5 | 1 << 13, RSH 9:  X >> 4 | X << 4 (in = 0)
+#define PK_US_RSH 0       // 5 bits: the right-shift unit's shift (U's low 5 bits: the word is the shift operand)
 #define PK_US_WPC 5       // 16-bit write value = return PC (else X)
 #define PK_US_W16 6       // write value 16-bit (else result8)
 #define PK_US_HIFIRST 7   // a 16-bit push: the slow bus path writes the high address first (PyBoy order)
-#define PK_US_FPOP 8      // F = m0 & 0xF0 (POP AF)
+#define PK_US_LOGIC 8     // result8 from the logic unit (loads: X = 0xFF AND Y), else adder / right unit
 #define PK_US_R16HL 9     // res16 = HL +- 1 (else adder)
 #define PK_US_SPW 10      // SP = res16
+#define PK_US_RIGHT 11    // result8 and C from the right-shift unit
 #define PK_US_LAND 12     // logic result includes X & Y (AND, OR)
 #define PK_US_LXOR 13     // logic result includes X ^ Y (XOR, OR)
-#define PK_US_HLINC 22    // 2 bits signed HL increment for (HL+)/(HL-)
+#define PK_US_JUMP 14     // control transfer to X + Y (+ pc + len for JR) when the condition holds
+#define PK_US_FY 16       // 8 bits, alone in their byte: F |= Y & FY (POP AF, DAA: 0xF0 of m0)
+#define PK_US_HLINC 24    // 2 bits signed HL increment for (HL+)/(HL-)
 #define PK_US_SPD 26      // 3 bits signed SP delta (PUSH/POP family), applied when the condition holds
+#define PK_CI_HSH 8u      // CI bits 0-4: H/C from carry bits 12/16 (ADD HL,rr)
+#define PK_CI_RMUL ((1u << 5) | (1u << 14))
+#define PK_CI_SMUL ((1u << 5) | (1u << 13))
+#define PK_RS_IN 13       // the shifted-in bit's position before the shift
 #define PK_UC_ENTRIES 515u
 #define PK_UC_INT 512u    // pseudo-op: interrupt dispatch (push PC, jump to the vector)
 #define PK_UC_IDLE 513u   // pseudo-op: halted / crashed CPU, 4 cycles
@@ -116,8 +130,8 @@ enum { PK_J_NONE = 0, PK_J_XY = 1, PK_J_JR = 2 };  // stored: target = X | Y (op
 
 // K word: constants
 #define PK_KB_YCONST 0    // 8 bits ORed into Y
-#define PK_KB_FKEEP 8     // 8 bits: F bits kept
-#define PK_KB_FCONST 16   // 8 bits: F bits set
+#define PK_KB_FKEEP 8     // 8 bits: F bits kept       (builder positions; the stored K word is
+#define PK_KB_FCONST 16   // 8 bits: F bits set         CM | FC << 8 | FK << 16, see above)
 #define PK_KB_CPUAND 24   // 4 bits: CPU state bits (IME HALT QUEUED CRASH) kept
 #define PK_KB_CPUOR 28    // 4 bits: CPU state bits set
 
@@ -526,11 +540,13 @@ static inline void pk_store_uop(uint32_t* e, PkUop o, bool real) {
     if (r8 == 3u) {
         const bool rdir = (o.u & pk_fld(1, PK_UB_RDIR)) != 0u;
         if (o.u & pk_fld(1, PK_UB_SWAP)) {
-            us |= pk_fld(1, PK_US_RIGHT) | pk_fld(1, PK_US_SWAP);
+            us |= pk_fld(1, PK_US_RIGHT) | pk_fld(9, PK_US_RSH);
+            ci = PK_CI_SMUL;
         } else if (rdir) {   // RRC RRCA RR RRA SRA SRL: shifted-in bit 0 / F.C / bit 0 (rotated out) / bit 7
             static const uint32_t rb[4] = {0u, 1u << 20, 1u << 0, 1u << 7};
-            us |= pk_fld(1, PK_US_RIGHT);
+            us |= pk_fld(1, PK_US_RIGHT) | pk_fld(6, PK_US_RSH);
             cw = rb[rbin];
+            ci = PK_CI_RMUL;
         } else {             // RLC RLCA RL RLA SLA: the adder, X + X + (0 / F.C / bit 7)
             static const uint32_t lb[4] = {0u, 1u << 20, 1u << 7, 0u};
             o.py = o.px;
@@ -544,17 +560,18 @@ static inline void pk_store_uop(uint32_t* e, PkUop o, bool real) {
         cw = 1u << 20;
         ci = 1u << 20;
     }
-    if (o.u & pk_fld(1, PK_UB_HC16)) us |= pk_fld(1, PK_US_HSH8);
-    if (o.u & pk_fld(1, PK_UB_FPOP)) us |= pk_fld(1, PK_US_FPOP);
+    if (o.u & pk_fld(1, PK_UB_HC16)) ci |= PK_CI_HSH;
     if (o.u & pk_fld(1, PK_UB_R16HL)) us |= pk_fld(1, PK_US_R16HL);
     if (o.u & pk_fld(1, PK_UB_SPW)) us |= pk_fld(1, PK_US_SPW);
-    us |= o.u & ((3u << PK_UB_HLINC) | (7u << PK_UB_SPD));   // same positions as PK_US_HLINC / PK_US_SPD
-    // flags: F' = (F & FK) | ((Z | H | C | FC) & FM)
-    const uint32_t fkeep = (o.k >> PK_KB_FKEEP) & 0xFFu, fconst = (o.k >> PK_KB_FCONST) & 0xFFu;
-    uint32_t fm = fconst;
-    if (o.u & pk_fld(1, PK_UB_FZ)) fm |= 0x80u;
-    if (o.u & pk_fld(1, PK_UB_FH)) fm |= 0x20u;
-    if (fcs != 0u) fm |= 0x10u;
+    us |= pk_fld((o.u >> PK_UB_HLINC) & 3u, PK_US_HLINC) | (o.u & (7u << PK_UB_SPD));   // SPD: same position
+    // flags: F' = ((Z | H | C) & CM) | FC | (F & FK) | (Y & FY)
+    uint32_t fkeep = (o.k >> PK_KB_FKEEP) & 0xFFu;
+    const uint32_t fconst = (o.k >> PK_KB_FCONST) & 0xFFu;
+    uint32_t cm = 0;
+    if (o.u & pk_fld(1, PK_UB_FZ)) cm |= 0x80u;
+    if (o.u & pk_fld(1, PK_UB_FH)) cm |= 0x20u;
+    if (fcs != 0u) cm |= 0x10u;
+    if (o.u & pk_fld(1, PK_UB_FPOP)) { us |= pk_fld(0xF0u, PK_US_FY); fkeep = 0; }   // F = m0 & 0xF0
     // operand sources -> ext-pool selectors (the register-pool selector is zeroed when unused);
     // a memory operand is m0 for one-byte reads, m0|m1 for two
     const bool rd2 = (o.d & pk_fld(1, PK_DB_RD2)) != 0u;
@@ -574,7 +591,7 @@ static inline void pk_store_uop(uint32_t* e, PkUop o, bool real) {
                                               pk_fld(1, PK_DB_DAA))) && (o.d & 3u) != 0u))
         e[PK_UE_D] |= pk_fld(1, PK_DB_NOFUSE);
     e[PK_UE_U] = us;
-    e[PK_UE_K] = fconst | (fkeep << 8) | (fm << 16) | (cpu_keep << 24) | (cpu_set << 28);
+    e[PK_UE_K] = cm | (fconst << 8) | (fkeep << 16) | (cpu_keep << 24) | (cpu_set << 28);
     const uint32_t len = o.d & 3u;
     const uint32_t succ = (e[PK_UE_D] & pk_fld(1, PK_DB_NOFUSE)) ? 0x0C0Du : (len | ((len + 1u) << 8));
     e[PK_UE_V] = succ | ((((o.d >> PK_DB_CYC) & 7u) * 4u) << 16) | ((((o.d >> PK_DB_XCYC) & 3u) * 4u) << 24);
@@ -604,25 +621,36 @@ static inline void pk_store_uop(uint32_t* e, PkUop o, bool real) {
 // own entry, which must therefore stay empty (length 0) — RST is a control transfer, never a
 // secondary op; tests/test_ucode_table.py checks both.  Entry, two uint4:
 //   a.x  X selector over w1:w0 (the pair, or a register into byte 0; JR: the F mask at F's byte)
-//   a.y  misc: length, cycles, delta, JR condition value, mask of the F bits the op writes
-//   a.z/a.w  writeback selectors of val2 = res16 | F' << 16 | res8 << 24 (as S0/S1)
+//   a.y  misc: length, cycles, delta, JR condition value
+//   a.z/a.w  writeback selectors of val2 = res16 | F' << 16 | res8 << 24 (as S0/S1); an entry that
+//        writes no flag takes F from w1 itself (S1 byte 2 = 0x02), as the not-fused case does
+//        (PK_S1_KEEP): what the flag unit computes for those is never looked at
 //   b.x  Y selector over w1:w0 (register operand), b.y immediate mask (Y |= n & b.y), b.z Y xor
 //        mask (0xFF: subtract), b.w control (PK_U2C_*)
 // datapath: r = X + (Y ^ b.z) + delta + carry-in; res = r, or the logic unit's X&Y / X^Y / X|Y;
 // flags Z from res, H/C from the adder's carry vector (^ flip, & mask), constants ORed in.
+// The flag unit works in place, at F's position in w1 (bits 20-23), on four masks that ride in bits
+// 20-23 of four words (PK_U2_FPOS; bits 16-19 of each are clear or meet F's zero low nibble, every
+// other bit of F' is garbage the writeback selector never takes):
+//   F' = (((H|C carries ^ FLIP) | Z) & MASK) | FCONST | (w1 & FK)
+//   MASK in b.w (the computed flags the op takes), FCONST in b.y, FLIP in b.z, FK (the flags kept) in
+//   a.x — w1 & a.x is the JR test's own operand.  The operand words' bits above 16 reach no result
+//   (8- and 16-bit sums; the selector byte FK makes of a.x's byte 2 yields 0xFF there).
 #define PK_U2B_LEN 0      // 2 bits length (0: no secondary op)
 #define PK_U2B_ONE 2      // 1: counts as an executed instruction
 #define PK_U2B_CYC 4      // 4 bits cycles (JR: not taken; at most 8)
 #define PK_U2B_DELTA 8    // 8 bits signed: added to Y (INC/DEC)
 #define PK_U2B_CV 16      // 8 bits: JR taken when (F & mask) == cv, the mask in byte 2 of the x word;
                           //         1 for every other entry (F's low nibble is 0: never)
-#define PK_U2B_FM 24      // 8 bits: F bits the op writes, the rest kept
 #define PK_U2_NONE_Y (1u << PK_U2B_CV)
+#define PK_U2_FPOS 16     // F's byte in w1: where the flag masks sit in a.x, b.y, b.z and b.w
+#define PK_S1_KEEP 0x03020100u   // w1 writeback selector: every byte, F included, from w1
 #define PK_U2C_USEC 0     // carry-in F.C (ADC, SBC)
 #define PK_U2C_SUBC 1     // carry-in ^ 1 (SUB, SBC, CP: X + ~Y + 1 [- C])
 #define PK_U2C_LOGIC 2    // res = logic unit
 #define PK_U2C_LA 3       // logic includes X & Y (AND, OR)
 #define PK_U2C_LX 4       // logic includes X ^ Y (XOR, OR, CPL)
+// (builder positions of pk_u2_entry's local ctl word; stored as the in-place masks above)
 #define PK_U2C_FCONST 8   // 8 bits: F bits set (N of SUB/DEC/CP, H of AND, CPL/SCF constants)
 #define PK_U2C_HCM 16     // 8 bits: F bits taken from the adder (H 0x20, C 0x10)
 #define PK_U2C_FLIP 24    // 8 bits: adder flags inverted (borrow = !carry)
@@ -688,15 +716,18 @@ static inline void pk_u2_entry(uint32_t* e, int op) {
             cv = op == 0x18 ? 0u : val[(op >> 3) & 3];
         }
     }
-    e[0] = sel;
+    // fm: the flags the op writes (Z computed when written; H/C computed under HCM, else constant)
+    const uint32_t fconst = (ctl >> PK_U2C_FCONST) & 0xFFu, hcm = (ctl >> PK_U2C_HCM) & 0xFFu, flip = (ctl >> PK_U2C_FLIP) & 0xFFu;
+    const uint32_t mask = (fm & PK_F_Z) | hcm, fk = fm ? (~fm & 0xF0u) : 0u;
+    e[0] = sel | (fk << PK_U2_FPOS);
     e[1] = (len << PK_U2B_LEN) | ((len ? 1u : 0u) << PK_U2B_ONE) | (cyc << PK_U2B_CYC)
-         | (((uint32_t)delta & 0xFFu) << PK_U2B_DELTA) | (cv << PK_U2B_CV) | (fm << PK_U2B_FM);
+         | (((uint32_t)delta & 0xFFu) << PK_U2B_DELTA) | (cv << PK_U2B_CV);
     e[2] = o.s0;
-    e[3] = o.s1;
+    e[3] = fm ? o.s1 : (o.s1 & 0xFF00FFFFu) | (PK_S1_KEEP & 0x00FF0000u);
     e[4] = ysel;
-    e[5] = imm;
-    e[6] = ysm;
-    e[7] = ctl;
+    e[5] = imm | (fconst << PK_U2_FPOS);
+    e[6] = ysm | (flip << PK_U2_FPOS);
+    e[7] = (ctl & 0xFFu) | (mask << PK_U2_FPOS);
 }
 
 static inline void pk_build_ucode(uint32_t* t /* PK_UC_WORDS */) {
