@@ -773,6 +773,76 @@ uint32_t pk_probe_count(const pk_handle* h);          /* 0 without a program */
 int pk_probe_eval(pk_handle* h, const uint8_t* mask_dev, uint32_t flags, uint32_t env0, uint32_t count,
                   double* rew_dev, uint8_t* term_dev, int32_t* feat_dev, void* stream);
 
+/* Tile view: the screen as 18 x 20 tile ids and object ids, computed on the device from the machine
+ * state a step leaves — the symbolic observation Game Boy RL feeds a policy (the visible tile matrix
+ * plus the sprite list), 360 or 720 small integers per env in the place of 23,040 grey bytes.  It
+ * needs nothing else: no PK_F_RENDER (a headless handle has it), no PK_F_REWARD, no bank.
+ *
+ * The tile view of an env is THE FRAME THE PPU WOULD DRAW IF THE REGISTERS HELD AT THE END OF THE STEP
+ * HAD HELD FOR THE WHOLE FRAME, sampled once per 8 x 8 screen cell: u16[n][P][18][20], plane 0 the
+ * background / window, plane 1 (P = 2, with PK_TILES_OBJ) the objects; 0xFFFF means "nothing".  It
+ * reads LCDC, SCY, SCX, WY, WX as the step left them, the VRAM image and the OAM image, all in
+ * integers.  It is not the pixels where a game writes scroll or LCDC registers mid-frame, puts
+ * more than ten objects on a line or toggles the window mid-frame (the window's line counter):
+ * that is the price of not rasterising.
+ *
+ * Plane 0, cell (r, c), sample pixel (x, y) = (8c, 8r):
+ *   LCDC.7 = 0 or LCDC.0 = 0      0xFFFF
+ *   window cell                   when LCDC.5 is set, y >= WY, WX <= 166 and x + 7 >= WX: map row
+ *                                 (y - WY) >> 3, map column (x + 7 - WX) >> 3, the map LCDC.6 selects
+ *                                 (0x9C00 when set, else 0x9800)
+ *   background cell               otherwise: map row ((y + SCY) & 255) >> 3, map column
+ *                                 ((x + SCX) & 255) >> 3, the map LCDC.3 selects
+ *   tile id                       with map byte t: t when LCDC.4 is set or t >= 128, else 256 + t — ids
+ *                                 run 0..383 and id * 16 is the tile's offset in VRAM
+ * Plane 1: all 0xFFFF when LCDC.7 = 0 or LCDC.1 = 0.  Otherwise OAM entry i = (Y, X, T, attr), i =
+ * 0..39, sits at oy = Y - 16, ox = X - 8 and its home cell is r = (oy + 4) >> 3, c = (ox + 4) >> 3
+ * (arithmetic shifts: the nearest cell; there is no ten-per-line limit).  An 8 x 8 object (LCDC.2 = 0)
+ * puts T into (r, c).  An 8 x 16 object puts T & 0xFE into (r, c) and T | 1 into (r + 1, c), the two
+ * values swapped when attr bit 6 (Y flip) is set.  A cell outside the 18 x 20 grid is dropped, each on
+ * its own.  Where several objects claim a cell the smaller X wins, then the lower i (the DMG
+ * priority rule).
+ *
+ * Mode: PK_TILES_ID stores the ids above.  PK_TILES_HASH with bits in 8..15 stores, in the place of
+ * every id (of both planes; 0xFFFF stays), a hash of the tile's 16 data bytes — games reload tile
+ * data, so an id is a slot and not a picture: with w0..w3 the little-endian dwords at VRAM offset
+ * id * 16 (objects: T * 16 of the tile they show),
+ *   h = mix((w0 | w1 << 32) ^ mix((w2 | w3 << 32) + 0x9E3779B97F4A7C15))
+ * in 64-bit arithmetic, mix being splitmix64's finaliser (pk_archive_explore states it), and the stored
+ * value is h & ((1 << bits) - 1).  Flips and palettes do not enter it.
+ *
+ * Key (optional): with v_i the i-th u16 of the env's view in output order, i = 0 .. P * 360 - 1,
+ *   key = mix(salt ^ XOR_i mix(v_i + (i + 1) * 0x9E3779B97F4A7C15))
+ * where salt = salt_dev[e], 0 without salt_dev.  The XOR makes the key independent of the order of
+ * the reduction.  As in pk_frame_keys the reserved key 0xFFFF...F is never produced (it becomes
+ * 0xFFFF...E), except that a salt of 0xFFFF...F ("no cell") gives the key 0xFFFF...F.
+ *
+ * pk_tiles_create (synchronous): once per handle, on any handle; mode is PK_TILES_ID (bits is
+ * ignored) or PK_TILES_HASH (bits 8..15), flags 0 or PK_TILES_OBJ.  The view starts as all 0xFFFF.  On
+ * failure (second call, unknown mode or flag bits, bits out of range, out of memory) the handle is
+ * unchanged.  pk_tiles_planes is P, 0 without a view; pk_tiles_ptr a device pointer the handle owns,
+ * valid until pk_destroy, NULL without a view.  A handle that never creates one makes exactly the
+ * launches and allocations it made before.
+ *
+ * pk_tiles_eval (one launch, stream-ordered, no host sync, no allocation): the envs of the range
+ * with mask_dev[e] != 0 (a NULL mask: every env of the range) get their rows of the view and, with
+ * keys_dev, their keys; every other env keeps both.  mask_dev is a device u8[n], salt_dev and keys_dev
+ * device u64[n], each may be NULL, all full size and indexed by env; salt_dev may be keys_dev.  The
+ * range follows pk_step_range's rule.  The view is a pure function of the machine state: the
+ * caller evaluates again after whatever replaces a machine (a reset, a load, a resume), and nothing
+ * of it travels in bank slots.  Nothing outside the rows and keys of [env0, env0 + count) is written, so
+ * disjoint ranges may run concurrently on different streams.  Bad arguments (no view, a range past
+ * n, an env0 that is no multiple of 64, count 0) are a negative code with pk_last_error, never a
+ * fault, and write nothing. */
+#define PK_TILES_ID 0u
+#define PK_TILES_HASH 1u
+#define PK_TILES_OBJ 1u           /* pk_tiles_create flag: plane 1, the objects */
+int pk_tiles_create(pk_handle* h, uint32_t mode, uint32_t bits, uint32_t flags);
+uint32_t pk_tiles_planes(const pk_handle* h);         /* 0 without a view */
+uint16_t* pk_tiles_ptr(pk_handle* h);                 /* device pointer, owned by the handle; NULL without */
+int pk_tiles_eval(pk_handle* h, const uint8_t* mask_dev, const uint64_t* salt_dev, uint64_t* keys_dev,
+                  uint32_t env0, uint32_t count, void* stream);
+
 /* Emulated instructions executed by the last pk_step, summed over envs (synchronous). */
 int pk_last_instr_count(pk_handle* h, uint64_t* out);
 

@@ -34,6 +34,9 @@ PK_PC_NONE, PK_PC_EQ, PK_PC_NE, PK_PC_GE, PK_PC_LE = 0, 1, 2, 3, 4
 PK_PROBE_REBASE_ONLY, PK_PROBE_SET = 1, 2
 PK_PROBE_MAX = 64
 PK_GEP_PROBES, PK_GEP_STACK = 1, 2
+PK_TILES_ID, PK_TILES_HASH = 0, 1
+PK_TILES_OBJ = 1
+TILE_ROWS, TILE_COLS = 18, 20
 HEAT_SHAPE = (444, 436)
 OBS_SHAPE = (72, 80, 4)
 # PK_ERR_* -> the exception the reference raises at that point (include/pokegym_amd.h)
@@ -62,7 +65,8 @@ EXPORTS = ("pk_create", "pk_destroy", "pk_last_error", "pk_abi_version", "pk_res
            "pk_counts_read", "pk_counts_clear",
            "pk_fstack_create", "pk_fstack_depth", "pk_fstack_scale", "pk_fstack_ptr", "pk_fstack_push",
            "pk_probe_create", "pk_probe_count", "pk_probe_eval",
-           "pk_bank_enable_generic_episodes", "pk_bank_generic_parts", "pk_bank_generic_episode_bytes")
+           "pk_bank_enable_generic_episodes", "pk_bank_generic_parts", "pk_bank_generic_episode_bytes",
+           "pk_tiles_create", "pk_tiles_planes", "pk_tiles_ptr", "pk_tiles_eval")
 
 
 class PkConfig(ctypes.Structure):
@@ -169,6 +173,7 @@ def bind(L):
     bind_fstack(L)
     bind_probes(L)
     bind_generic(L)
+    bind_tiles(L)
 
 
 def bind_v2(L):
@@ -315,6 +320,18 @@ def bind_generic(L):
     L.pk_bank_generic_parts.restype = ctypes.c_uint32
     L.pk_bank_generic_episode_bytes.argtypes = [vp]
     L.pk_bank_generic_episode_bytes.restype = ctypes.c_uint64
+
+
+def bind_tiles(L):
+    """argtypes of the tile view (additive to ABI v12; shared with the host-simulation test build)."""
+    vp = ctypes.c_void_p
+    u32 = ctypes.c_uint32
+    L.pk_tiles_create.argtypes = [vp, u32, u32, u32]
+    L.pk_tiles_planes.argtypes = [vp]
+    L.pk_tiles_planes.restype = u32
+    L.pk_tiles_ptr.argtypes = [vp]
+    L.pk_tiles_ptr.restype = vp
+    L.pk_tiles_eval.argtypes = [vp, vp, vp, vp, u32, u32, vp]
 
 
 def check(rc: int, what: str):

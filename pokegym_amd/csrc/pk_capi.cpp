@@ -54,6 +54,7 @@ hipError_t pk_launch_cell_keys(const uint8_t* mem, uint32_t sh, uint32_t shift, 
 hipError_t pk_launch_frame_keys(const PkCellArgs& a, hipStream_t s);
 hipError_t pk_launch_fstack(const PkStackArgs& a, hipStream_t s);
 hipError_t pk_launch_probe(const PkProbeArgs& a, hipStream_t s);
+hipError_t pk_launch_tiles(const PkTilesArgs& a, hipStream_t s);
 hipError_t pk_launch_gep_move(const PkGepArgs& a, hipStream_t s);
 hipError_t pk_launch_cnt_update(const PkCountArgs& a, hipStream_t s);
 hipError_t pk_launch_cnt_add(const PkCountArgs& a, hipStream_t s);
@@ -355,6 +356,10 @@ struct pk_handle {
     uint32_t pr_m = 0;
     pk_probe* pr_prog = nullptr;
     uint32_t* pr_state = nullptr;
+    // tile view (pk_tiles_create; pk_layout.h PkTilesArgs), tl_planes = 0 without one: u16[n][P][18][20];
+    // tl_bits = 0 in PK_TILES_ID mode
+    uint32_t tl_planes = 0, tl_bits = 0;
+    uint16_t* tl_out = nullptr;
     // profiling: 4 events per profiled step (start, after K1, after K2, after K4+K3)
     bool prof = false;
     std::vector<hipEvent_t> ev_pool;
@@ -1810,6 +1815,43 @@ int pk_probe_eval(pk_handle* h, const uint8_t* mask, uint32_t flags, uint32_t en
     a.m = h->pr_m; a.npad = h->npad; a.env0 = env0; a.env1 = env0 + count; a.ilv_sh = h->ilv_sh;
     a.rebase_only = flags & PK_PROBE_REBASE_ONLY; a.set = (flags & PK_PROBE_SET) ? 1u : 0u;
     HIPCHK(pk_launch_probe(a, (hipStream_t)stream));
+    return 0;
+}
+
+// ---- tile view ----------------------------------------------------------------------------------
+
+uint32_t pk_tiles_planes(const pk_handle* h) { return h ? h->tl_planes : 0; }
+uint16_t* pk_tiles_ptr(pk_handle* h) { return h ? h->tl_out : nullptr; }
+
+int pk_tiles_create(pk_handle* h, uint32_t mode, uint32_t bits, uint32_t flags) {
+    if (!h) return fail(-EINVAL, "null handle");
+    if (h->tl_planes) return fail(-EEXIST, "the handle already has a tile view of %u planes", h->tl_planes);
+    if (mode != PK_TILES_ID && mode != PK_TILES_HASH) return fail(-EINVAL, "unknown tile view mode %u", mode);
+    if (mode == PK_TILES_HASH && (bits < 8 || bits > 15)) return fail(-EINVAL, "PK_TILES_HASH takes bits in 8..15, not %u", bits);
+    if (flags & ~PK_TILES_OBJ) return fail(-EINVAL, "unknown flags 0x%x", flags);
+    HIPCHK(hipSetDevice(h->device));
+    const uint32_t planes = (flags & PK_TILES_OBJ) ? 2u : 1u;
+    const size_t bytes = (size_t)h->n * planes * PK_TILE_CELLS * sizeof(uint16_t);
+    Stage st(h);
+    st.want(h->tl_out, bytes, 0xFF);
+    if (hipError_t e = st.run())
+        return fail(-ENOMEM, "tile view of %u planes (%zu bytes): %s", planes, bytes, hipGetErrorString(e));
+    st.commit();
+    h->tl_planes = planes; h->tl_bits = mode == PK_TILES_HASH ? bits : 0u;
+    return 0;
+}
+
+int pk_tiles_eval(pk_handle* h, const uint8_t* mask, const uint64_t* salt, uint64_t* keys, uint32_t env0, uint32_t count,
+                  void* stream) {
+    int rc;
+    if ((rc = check_range(h, env0, count))) return rc;
+    if (!h->tl_planes) return fail(-ENOENT, "the handle has no tile view (pk_tiles_create)");
+    HIPCHK(hipSetDevice(h->device));
+    PkTilesArgs a;
+    a.mem = h->mem; a.regs = h->regs; a.mask = mask; a.salt = salt; a.keys = keys; a.out = h->tl_out;
+    a.npad = h->npad; a.env0 = env0; a.env1 = env0 + count; a.ilv_sh = h->ilv_sh;
+    a.planes = h->tl_planes; a.bits = h->tl_bits;
+    HIPCHK(pk_launch_tiles(a, (hipStream_t)stream));
     return 0;
 }
 

@@ -1210,6 +1210,186 @@ hipError_t pk_launch_probe(const PkProbeArgs& a, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Tile view (pk_tiles_eval): the screen as 18 x 20 tile ids (or hashes of the tiles' data) and the
+// object plane, from the registers, the VRAM image and the OAM image a step leaves
+// (include/pokegym_amd.h states the model).  A workgroup of PK_TILES_WG threads takes PK_TILES_ENVS
+// neighbouring envs; thread t works for env t % PK_TILES_ENVS on the cells t / PK_TILES_ENVS,
+// + PK_TILES_SLOTS, ...  So 16 neighbouring lanes hold the 16 envs of one cell: envs in the same game
+// state read 16 consecutive bytes of the interleaved image (pk_img_off; any interleave works, a
+// narrower one than 16 splits the run), and the cells of a wave's four lane groups are neighbours
+// in the map.  The registers come from the SoA arrays.
+//   1. slot 0 of every env reads the mask byte and, if the env takes part, LCD0 / LCD1 into LDS.
+//   2. every thread clears its cells' object words, stages its share of the env's 160 OAM bytes
+//      (once), and computes the BG / window plane of its cells into LDS: the map bytes of all its
+//      cells first, then in hash mode the 16 data bytes of each.
+//   3. a thread per object takes the object's one or two cells with an LDS atomicMin of
+//      X << 8 | index: the smaller X wins, then the lower index, whatever the order of the threads.
+//   4. every thread turns its cells' winners into the plane's values; the key terms are XORed per
+//      thread and reduced through LDS.
+//   5. the view leaves as consecutive dwords: an env's planes are one run of P * 720 bytes (rows of
+//      40 bytes back to back), and the envs of a workgroup follow each other.
+// An env that is masked out costs its mask byte: its threads issue no other load and no store.
+// Every barrier is reached by every thread (no early return), and the kernel is launched under a
+// PK_K1_KERNEL_ name, so the host-simulation build joins its threads at them.  LDS rows are padded
+// to an odd number of dwords.
+#define PK_TILES_NC ((PK_TILE_CELLS + PK_TILES_SLOTS - 1u) / PK_TILES_SLOTS)   // cells per thread, 23
+#define PK_TILES_LD0 (PK_TILE_CELLS + 2u)     // u16 per env of the BG plane's row: 181 dwords
+#define PK_TILES_LD1 (PK_TILE_CELLS + 1u)     // u32 per env of the object plane's row
+#define PK_TILES_OAMLD 41u                    // u32 per env of the staged OAM: 40 entries and a pad
+
+// the hash of the 16 data bytes of tile `id` (VRAM offset id * 16), cut to `bits` bits
+__device__ __forceinline__ u32 pk_tiles_hash(const u8* img, u32 sh, u32 id, u32 bits) {
+    const u8* p = img + ((size_t)(PK_P_VRAM + id * 16u) << sh);
+    u32 w[4];
+#pragma unroll
+    for (u32 j = 0; j < 4u; j++)
+        w[j] = (u32)p[(size_t)(4u * j) << sh] | (u32)p[(size_t)(4u * j + 1u) << sh] << 8
+             | (u32)p[(size_t)(4u * j + 2u) << sh] << 16 | (u32)p[(size_t)(4u * j + 3u) << sh] << 24;
+    const u64 h = pk_arch_mix(((u64)w[0] | (u64)w[1] << 32) ^ pk_arch_mix(((u64)w[2] | (u64)w[3] << 32) + PK_CELL_GOLD));
+    return (u32)h & ((1u << bits) - 1u);
+}
+
+#define PK_K1_KERNEL_TILES pk_tiles_kernel
+__global__ void __launch_bounds__(PK_TILES_WG) pk_tiles_kernel(PkTilesArgs A) {
+    __shared__ uint16_t bg[PK_TILES_ENVS * PK_TILES_LD0];
+    __shared__ u32 obj[PK_TILES_ENVS * PK_TILES_LD1];   // X << 8 | index of the cell's winner, then its value
+    __shared__ u32 oam[PK_TILES_ENVS * PK_TILES_OAMLD];
+    __shared__ u64 red[PK_TILES_WG];
+    __shared__ u32 lcd[2u * PK_TILES_ENVS];
+    __shared__ u8 takes[PK_TILES_ENVS];
+    const u32 tid = threadIdx.x, el = tid % PK_TILES_ENVS, slot = tid / PK_TILES_ENVS, sh = A.ilv_sh;
+    const u32 base = A.env0 + blockIdx.x * PK_TILES_ENVS, e = base + el;
+    const bool two = A.planes > 1u;
+
+    if (slot == 0u) {
+        const bool t = e < A.env1 && (!A.mask || A.mask[e] != 0);   // t implies e < env1: the env's loads
+        takes[el] = t;                                              // stay inside the arrays
+        lcd[el] = t ? A.regs[(size_t)PK_R_LCD0 * A.npad + e] : 0u;
+        lcd[PK_TILES_ENVS + el] = t ? A.regs[(size_t)PK_R_LCD1 * A.npad + e] : 0u;
+    }
+    __syncthreads();
+    const bool part = takes[el] != 0;
+    const u32 lcdc = lcd[el] & 0xFFu, l1 = lcd[PK_TILES_ENVS + el];
+    const u32 scy = l1 & 0xFFu, scx = (l1 >> 8) & 0xFFu, wy = (l1 >> 16) & 0xFFu, wx = l1 >> 24;
+    const bool lcd_on = (lcdc & 0x80u) != 0, obj_on = two && part && lcd_on && (lcdc & 0x02u);
+    const u8* img = A.mem + pk_img_off(part ? e : base, 0u, sh);
+    u64 acc = 0;
+
+    if (two) {
+#pragma unroll
+        for (u32 k = 0; k < PK_TILES_NC; k++) {
+            const u32 cell = slot + k * PK_TILES_SLOTS;
+            if (cell < PK_TILE_CELLS) obj[el * PK_TILES_LD1 + cell] = 0xFFFFFFFFu;
+        }
+        if (obj_on) {       // 160 bytes over the env's 16 threads
+            u8* ob = reinterpret_cast<u8*>(oam + el * PK_TILES_OAMLD);
+#pragma unroll
+            for (u32 k = 0; k < 160u / PK_TILES_SLOTS; k++) {
+                const u32 b = slot + k * PK_TILES_SLOTS;
+                ob[b] = img[(size_t)(PK_P_OAM + b) << sh];
+            }
+        }
+    }
+    {
+        const bool bg_on = part && lcd_on && (lcdc & 0x01u);
+        const bool win_on = (lcdc & 0x20u) != 0 && wx <= 166u;
+        u32 id[PK_TILES_NC];
+#pragma unroll
+        for (u32 k = 0; k < PK_TILES_NC; k++) {
+            const u32 cell = slot + k * PK_TILES_SLOTS;
+            id[k] = PK_TILE_NONE;
+            if (!bg_on || cell >= PK_TILE_CELLS) continue;
+            const u32 y = cell / PK_TILE_COLS * 8u, x = cell % PK_TILE_COLS * 8u;
+            const bool win = win_on && y >= wy && x + 7u >= wx;
+            const u32 row = win ? (y - wy) >> 3 : ((y + scy) & 255u) >> 3;
+            const u32 col = win ? (x + 7u - wx) >> 3 : ((x + scx) & 255u) >> 3;
+            const u32 map = (lcdc & (win ? 0x40u : 0x08u)) ? 0x1C00u : 0x1800u;
+            const u32 t = img[(size_t)(PK_P_VRAM + map + row * 32u + col) << sh];
+            id[k] = (lcdc & 0x10u) || t >= 128u ? t : 256u + t;
+        }
+#pragma unroll
+        for (u32 k = 0; k < PK_TILES_NC; k++) {
+            const u32 cell = slot + k * PK_TILES_SLOTS;
+            if (cell >= PK_TILE_CELLS) continue;
+            u32 v = id[k];
+            if (A.bits && v != PK_TILE_NONE) v = pk_tiles_hash(img, sh, v, A.bits);
+            bg[el * PK_TILES_LD0 + cell] = (uint16_t)v;
+            acc ^= pk_arch_mix((u64)v + (u64)(cell + 1u) * PK_CELL_GOLD);
+        }
+    }
+    __syncthreads();
+
+    if (two) {
+        const u32 tall = lcdc & 0x04u;
+        for (u32 i = slot; i < 40u; i += PK_TILES_SLOTS) {
+            if (!obj_on) continue;
+            const u32 o = oam[el * PK_TILES_OAMLD + i];          // Y | X << 8 | T << 16 | attr << 24
+            const int r = ((int)(o & 0xFFu) - 16 + 4) >> 3, c = ((int)((o >> 8) & 0xFFu) - 8 + 4) >> 3;
+            if (c < 0 || c >= (int)PK_TILE_COLS) continue;
+            const u32 claim = ((o >> 8) & 0xFFu) << 8 | i;
+            u32* rowp = obj + el * PK_TILES_LD1 + c;
+            if (r >= 0 && r < (int)PK_TILE_ROWS) atomicMin(rowp + r * (int)PK_TILE_COLS, claim);
+            if (tall && r + 1 >= 0 && r + 1 < (int)PK_TILE_ROWS) atomicMin(rowp + (r + 1) * (int)PK_TILE_COLS, claim);
+        }
+        __syncthreads();
+        const u32 tallv = lcdc & 0x04u;
+#pragma unroll 1
+        for (u32 k = 0; k < PK_TILES_NC; k++) {
+            const u32 cell = slot + k * PK_TILES_SLOTS;
+            if (cell >= PK_TILE_CELLS) continue;
+            const u32 w = obj[el * PK_TILES_LD1 + cell];
+            u32 v = PK_TILE_NONE;
+            if (w != 0xFFFFFFFFu) {     // only cells of an env with obj_on are ever claimed
+                const u32 o = oam[el * PK_TILES_OAMLD + (w & 0xFFu)];
+                v = (o >> 16) & 0xFFu;
+                if (tallv) {
+                    const int r = ((int)(o & 0xFFu) - 16 + 4) >> 3;
+                    const bool top = (int)(cell / PK_TILE_COLS) == r, flip = (o >> 30) & 1u;
+                    v = top != flip ? v & 0xFEu : v | 1u;
+                }
+                if (A.bits) v = pk_tiles_hash(img, sh, v, A.bits);
+            }
+            obj[el * PK_TILES_LD1 + cell] = v;
+            acc ^= pk_arch_mix((u64)v + (u64)(PK_TILE_CELLS + cell + 1u) * PK_CELL_GOLD);
+        }
+    }
+    red[tid] = acc;
+    __syncthreads();
+
+    // the view: dword d of an env's P * 180; the keys: slot 0 XORs its env's 16 partial words
+    const u32 per = A.planes * (PK_TILE_CELLS / 2u);
+    u32* out = reinterpret_cast<u32*>(A.out);
+    for (u32 q = tid; q < PK_TILES_ENVS * per; q += PK_TILES_WG) {
+        const u32 row = q / per, d = q % per;
+        if (!takes[row]) continue;
+        u32 v;
+        if (d < PK_TILE_CELLS / 2u) {
+            const uint16_t* p = bg + row * PK_TILES_LD0 + 2u * d;
+            v = (u32)p[0] | (u32)p[1] << 16;
+        } else {
+            const u32* p = obj + row * PK_TILES_LD1 + 2u * (d - PK_TILE_CELLS / 2u);
+            v = p[0] | p[1] << 16;
+        }
+        out[(size_t)(base + row) * per + d] = v;
+    }
+    if (A.keys && slot == 0u && part) {
+        u64 x = 0;
+        for (u32 j = 0; j < PK_TILES_SLOTS; j++) x ^= red[j * PK_TILES_ENVS + el];
+        const u64 salt = A.salt ? A.salt[e] : 0;
+        u64 key = pk_arch_mix(salt ^ x);
+        if (key == PK_ARCH_NOKEY) key = PK_ARCH_NOKEY - 1u;
+        if (A.salt && salt == PK_ARCH_NOKEY) key = PK_ARCH_NOKEY;   // "no cell" passes through
+        A.keys[e] = key;
+    }
+}
+
+hipError_t pk_launch_tiles(const PkTilesArgs& a, hipStream_t s) {
+    const u32 count = a.env1 - a.env0;
+    hipLaunchKernelGGL(PK_K1_KERNEL_TILES, dim3((count + PK_TILES_ENVS - 1u) / PK_TILES_ENVS), dim3(PK_TILES_WG), 0, s, a);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
 // Generic episode mover (pk_bank_checkpoint / pk_bank_resume on a handle without the reward stack;
 // pk_layout.h PkGepArgs): the generic episode part of the envs on the range's bank list <-> their
 // validated slots, shaped like pk_ep_move_kernel.  A stack row is linear on both sides, so a

@@ -433,3 +433,29 @@ struct PkGepArgs {
     uint32_t save;               // 1 = checkpoint (env -> slot), 0 = resume (slot -> env)
     uint32_t items;              // upper bound of listed envs (the range's size): sizes the grid
 };
+
+// Tile view (pk_tiles_*): per env P planes (BG / window, objects) of PK_TILE_ROWS x PK_TILE_COLS u16
+// values, u16[n][P][18][20].  A workgroup of PK_TILES_WG threads takes PK_TILES_ENVS neighbouring envs
+// (a sub-block of the image, or a part of one); thread t works for env t % PK_TILES_ENVS on the
+// cells t / PK_TILES_ENVS, + PK_TILES_SLOTS, ...: neighbouring lanes hold neighbouring envs of one cell.
+#define PK_TILE_ROWS (PK_ROWS / 8u)           // 18
+#define PK_TILE_COLS (PK_COLS / 8u)           // 20
+#define PK_TILE_CELLS (PK_TILE_ROWS * PK_TILE_COLS)
+#define PK_TILE_NONE 0xFFFFu
+#define PK_TILES_WG 256u
+#define PK_TILES_ENVS 16u
+#define PK_TILES_SLOTS (PK_TILES_WG / PK_TILES_ENVS)
+
+struct PkTilesArgs {
+    const uint8_t* mem;          // lane-interleaved RAM images
+    const uint32_t* regs;        // K1 lane registers [PK_NREGS][npad]: PK_R_LCD0, PK_R_LCD1
+    const uint8_t* mask;         // caller's [n] or null
+    const uint64_t* salt;        // caller's [n] or null
+    uint64_t* keys;              // caller's [n] or null
+    uint16_t* out;               // [n][planes][18][20]
+    uint32_t npad;
+    uint32_t env0, env1;
+    uint32_t ilv_sh;
+    uint32_t planes;             // 1, or 2 with PK_TILES_OBJ
+    uint32_t bits;               // 0 = PK_TILES_ID, else the hash bits of PK_TILES_HASH (8..15)
+};

@@ -589,6 +589,42 @@ class BatchedEmulator:
                                     self._full(rewards, torch.float64, "rewards"),
                                     self._full(terminals, torch.uint8, "terminals"), fp, self._stream()), "pk_probe_eval")
 
+    # -- tile view (stream-ordered except create) ------------------------------------------
+    def tiles_create(self, mode: str = "id", bits: int = 12, objects: bool = True):
+        """Give the handle a tile view: per env the screen as 18 x 20 tile ids (mode "id") or `bits`-bit
+        hashes of the tiles' data (mode "hash", bits 8..15), with objects=True a second plane of object
+        tiles (pk_tiles_create; once, synchronous; any handle, render=False included).  `tiles` is the
+        tensor, all -1 ("nothing", 0xFFFF) until the first tiles_eval."""
+        if mode not in ("id", "hash"):
+            raise ValueError('tile view mode must be "id" or "hash"')
+        check(self._L.pk_tiles_create(self._h, _native.PK_TILES_HASH if mode == "hash" else _native.PK_TILES_ID, int(bits),
+                                      _native.PK_TILES_OBJ if objects else 0), "pk_tiles_create")
+        self._tiles = self._view(self._L.pk_tiles_ptr(self._h),
+                                 (self.n, self.tile_planes, _native.TILE_ROWS, _native.TILE_COLS), "<i2")
+
+    @property
+    def tile_planes(self) -> int:
+        """Planes of the tile view (pk_tiles_planes): 1, 2 with objects, 0 without tiles_create."""
+        return int(self._L.pk_tiles_planes(self._h))
+
+    @property
+    def tiles(self) -> torch.Tensor | None:
+        """The tile view, an int16 (n, P, 18, 20) view of the handle's buffer (pk_tiles_ptr; the u16
+        values as int16, so "nothing" is -1); None without tiles_create."""
+        return getattr(self, "_tiles", None)
+
+    def tiles_eval(self, mask: torch.Tensor | None = None, salt: torch.Tensor | None = None,
+                   keys: torch.Tensor | None = None, env0: int = 0, count: int | None = None):
+        """Evaluate the tile view of the envs of the range in one launch (pk_tiles_eval, on the current
+        stream).  mask: a full-size uint8 (n,) tensor; only the envs with mask[e] != 0 are written (no
+        mask: the whole range).  keys: an int64 (n,) tensor that receives the 64-bit key of each
+        written env's view, salt: int64 (n,) words mixed into the keys (`keys` itself will do; a salt
+        of -1, "no cell", stays -1).  Returns `tiles`."""
+        count = self.n - env0 if count is None else count
+        check(self._L.pk_tiles_eval(self._h, self._full(mask, torch.uint8, "mask"), self._full(salt, torch.int64, "salt"),
+                                    self._full(keys, torch.int64, "keys"), env0, count, self._stream()), "pk_tiles_eval")
+        return self.tiles
+
     # -- action trajectories (stream-ordered except enable) -------------------------------
     def traj_enable(self):
         """Record every env's actions from here on (pk_traj_enable; once, synchronous).  Call it
@@ -793,6 +829,7 @@ class BatchedEmulator:
             self.errors = None
             self.info = self.info_flag = self.heatmap = self.info_bits = None
             self._stack = None
+            self._tiles = None
             self._L.pk_destroy(self._h)
             self._h = None
 

@@ -51,11 +51,13 @@ def _read(path_or_bytes):
         return f.read()
 
 
-def _key_args(what: str, key, frame, render: bool):
-    """Validate a key choice ("ram", "frame" or "frame+ram") and its (bw, bh, levels); what = the
-    argument prefix, "archive" or "novelty"."""
-    if key not in ("ram", "frame", "frame+ram"):
-        raise ValueError(f'{what}_key must be "ram", "frame" or "frame+ram", not {key!r}')
+def _key_args(what: str, key, frame, render: bool, tiles: bool = False):
+    """Validate a key choice ("ram", "frame", "frame+ram" or "tiles") and its (bw, bh, levels); what = the
+    argument prefix, "archive" or "novelty"; tiles = the env has a tile view."""
+    if key not in ("ram", "frame", "frame+ram", "tiles"):
+        raise ValueError(f'{what}_key must be "ram", "frame", "frame+ram" or "tiles", not {key!r}')
+    if key == "tiles" and not tiles:
+        raise ValueError(f'{what}_key="tiles" is the tile view\'s key: the env needs tile_view=')
     try:
         bw, bh, levels = (int(v) for v in frame)
     except (TypeError, ValueError):
@@ -63,7 +65,7 @@ def _key_args(what: str, key, frame, render: bool):
     if bw not in (8, 16, 32, 40, 80, 160) or bh not in (8, 16, 24, 48, 72, 144) or not 2 <= levels <= 256:
         raise ValueError(f"{what}_frame = (bw, bh, levels): bw a multiple of 8 that divides 160, bh one that "
                          "divides 144, levels in 2..256")
-    if key != "ram" and not render:
+    if key not in ("ram", "tiles") and not render:
         raise ValueError(f'{what}_key="{key}" reads the screen: the emulator needs render=True')
     return key, (bw, bh, levels)
 
@@ -322,7 +324,8 @@ class VecEnv:
                  record_trajectories: bool = False, archive_exchange: bool = False, archive_key: str = "ram",
                  archive_frame=(16, 16, 8), novelty_log2: int = 0, novelty_beta: float = 1.0, novelty_key: str = "frame",
                  novelty_frame=(16, 16, 8), frame_stack: int = 0, stack_scale: int = 2, stack_layout: str = "chw",
-                 stack_mode: str = "mean", probes=None, probe_features: bool = False):
+                 stack_mode: str = "mean", probes=None, probe_features: bool = False, tile_view: str | None = None,
+                 tile_bits: int = 12, tile_objects: bool = True):
         """reward=False: the screen-obs env of configs[3] — obs is the (144, 160) u8 screen; without
         probes= or novelty_log2= the rewards are 0 and episodes end at max_episode_steps.
         power_on=True starts (and resets) every env from the cartridge's power-on state instead of
@@ -414,7 +417,20 @@ class VecEnv:
         the frame stack's refill: without bank_episodes="generic" the probe state does not travel through
         the bank, a resumed "newmax" starts again from the current value.  probe_features=True also keeps the probe values:
         probe_values is int32 (num_envs, m), the values every env's last step ended on (probe_space).
-        With None nothing is allocated or launched."""
+        With None nothing is allocated or launched.
+
+        tile_view="id" or "hash" (None = off) keeps the symbolic observation of every env on the device
+        (pk_tiles_*): the screen as 18 x 20 background / window tile ids and, with tile_objects, a second
+        plane of object tiles — or, with "hash", tile_bits-bit (8..15) hashes of the tiles' data, which
+        survive a game's reloading of tile data — int16 (P, 18, 20), -1 = nothing (tile_space).  It is
+        computed from the registers, VRAM and OAM a step leaves, never from pixels, so it works with a
+        headless emulator (render=False), and it is not the pixels where a game writes scroll or LCDC
+        mid-frame.  tile_obs() returns it.  Each sub-batch evaluates once per step, on its own stream and
+        in one launch, after the auto-reset (a finished env shows the first state of its next episode);
+        reset(), load_from_bank, resume_from_bank, fork, archive_explore and load_state evaluate the
+        envs whose machine they replaced.  archive_key="tiles" and novelty_key="tiles" use the view's
+        64-bit key: two envs are in one cell exactly when their views are equal.  With None nothing is
+        allocated or launched."""
         self.batch_size = batch_size or num_envs
         self.num_batches, rest = divmod(num_envs, self.batch_size)
         if rest:
@@ -464,6 +480,16 @@ class VecEnv:
             self.probe_space = spaces.probe_space(len(self.probes))
             if probe_features:
                 self._probe_feat = torch.zeros((n_phys, len(self.probes)), dtype=torch.int32, device=self.device)
+        # tile view (pk_tiles_*): nothing is allocated or called with tile_view=None
+        self.tile_view = tile_view
+        self.tile_space = None
+        if tile_view is not None:
+            if tile_view not in ("id", "hash"):
+                raise ValueError(f'tile_view must be "id", "hash" or None, not {tile_view!r}')
+            if tile_view == "hash" and not 8 <= int(tile_bits) <= 15:
+                raise ValueError("tile_bits must be 8..15")
+            self.emu.tiles_create(tile_view, tile_bits, bool(tile_objects))
+            self.tile_space = spaces.tile_space(self.emu.tile_planes)
         self.single_action_space = spaces.action_space()
         self.env_ids = torch.arange(env_offset, env_offset + num_envs, device=self.device)
         self.masks = torch.ones(num_envs, dtype=torch.bool, device=self.device)
@@ -516,11 +542,12 @@ class VecEnv:
             raise ValueError("fork_slots needs bank_episodes=True")
         self.archive_cells, self.archive_shift = int(archive_cells), int(archive_shift)
         self.archive_key, self.archive_frame = _key_args("archive", archive_key, archive_frame,
-                                                         getattr(emulator, "render", True))
+                                                         getattr(emulator, "render", True), tile_view is not None)
         # count-based novelty bonus (pk_counts_*): nothing is allocated or called with novelty_log2 = 0
         self.novelty_log2, self.novelty_beta = int(novelty_log2), float(novelty_beta)
         self.novelty_key, self.novelty_frame = _key_args("novelty", novelty_key, novelty_frame,
-                                                         not self.novelty_log2 or getattr(emulator, "render", True))
+                                                         not self.novelty_log2 or getattr(emulator, "render", True),
+                                                         tile_view is not None)
         self._nov_keys = self._nov_counts = self._nov_bonus = None
         # per sub-batch of the pipeline: 0 = nothing owed, 1 = sent, its keys not counted yet (recv()
         # counts them), 2 = counted by a flush, recv() still owes its bonus to the returned rewards
@@ -624,16 +651,19 @@ class VecEnv:
         self._join_streams()
         m = self._bank_map(envs, slots)
         self.emu.bank_load(m)
-        if self.frame_stack or self.probes is not None:
+        if self.frame_stack or self.probes is not None or self.tile_view:
             self._machines_replaced(((m >= 0) & (m < self.emu.bank_slots)).to(torch.uint8))
 
-    def _machines_replaced(self, mask: torch.Tensor):
+    def _machines_replaced(self, mask: torch.Tensor, carried: bool = False):
         """The envs with mask[e] != 0 (uint8, emulator order) run another machine from here on: their
-        frame stacks start over and their probes are rebased, on the current stream."""
-        if self.frame_stack:
+        frame stacks start over and their probes are rebased (not with carried: generic episode parts
+        brought both along), and their tile views are evaluated again, on the current stream."""
+        if self.frame_stack and not carried:
             self.emu.stack_push(mask, fill_only=True)
-        if self.probes is not None:
+        if self.probes is not None and not carried:
             self.emu.probes_eval(mask, rebase_only=True, features=self._probe_feat)
+        if self.tile_view:
+            self.emu.tiles_eval(mask)
 
     def _carried(self) -> dict:
         """Everything of an episode that this class keeps per env and that travels through a bank slot:
@@ -698,10 +728,10 @@ class VecEnv:
         # generic: stack rows and probe words came with the slot (and the feature rows with the ledger:
         # an evaluation would pay reward), so no refill and no rebase; else the resumed envs start a
         # history of their own
-        if not self._generic and (self.frame_stack or self.probes is not None):
+        if self.tile_view or (not self._generic and (self.frame_stack or self.probes is not None)):
             m = torch.zeros(self.emu.n, dtype=torch.uint8, device=self.device)
             m[self.phys(envs)] = ok.to(torch.uint8)
-            self._machines_replaced(m)
+            self._machines_replaced(m, carried=self._generic)
 
     def fork(self, dst_envs, src_envs, check: bool = True):
         """Copy the running episode of env src_envs[i] over env dst_envs[i]: every distinct source
@@ -751,6 +781,11 @@ class VecEnv:
         """The keys of kind "ram", "frame" (frame = (bw, bh, levels)) or "frame+ram" — the second salted
         with the first — of emulator envs [env0, env0 + count) into out (None: a new tensor), on the
         current stream."""
+        if kind == "tiles":
+            if out is None:
+                out = torch.zeros(self.emu.n, dtype=torch.int64, device=self.device)
+            self.emu.tiles_eval(keys=out, env0=env0, count=count)
+            return out
         salt = None
         if kind != "frame":
             salt = self.emu.cell_keys(self.archive_shift, out=out, env0=env0, count=count)
@@ -804,8 +839,8 @@ class VecEnv:
         mask = self._physical(torch.as_tensor(mask, device=self.device) != 0, 0, torch.uint8)
         self.emu.archive_explore(mask, out=self._arch_out)
         # the envs that resumed: the device's own answer, rejects excluded (generic parts carry both)
-        if (self.frame_stack or self.probes is not None) and not self._generic:
-            self._machines_replaced((self._arch_out >= 0).to(torch.uint8))
+        if self.tile_view or ((self.frame_stack or self.probes is not None) and not self._generic):
+            self._machines_replaced((self._arch_out >= 0).to(torch.uint8), carried=self._generic)
         drawn = self._logical(self._arch_out).long()
         ok, values = self._ledger.fetch(drawn)      # ok: drawn >= 0 and the slot holds an episode
         self._scatter(values, ok)
@@ -986,6 +1021,8 @@ class VecEnv:
             obs = self._logical(self.emu.stack_push(fill_only=True))
         if self.probes is not None:
             self.emu.probes_eval(rebase_only=True, features=self._probe_feat)
+        if self.tile_view:
+            self.emu.tiles_eval()
         self.t = 0
         self._log_wait = 0
         if self.sticky_errors is not None:
@@ -1110,6 +1147,8 @@ class VecEnv:
             self.emu.probes_eval(self.emu.terminals, rebase_only=True, env0=psl.start, count=self.batch_size)
         if self.frame_stack:        # one launch: the finished envs fill from their reset frame, the others push
             obs = self.emu.stack_push(self.emu.terminals, env0=psl.start, count=self.batch_size)[psl]
+        if self.tile_view:          # one launch: the state the step ended on, or the reset state of a finished env
+            self.emu.tiles_eval(env0=psl.start, count=self.batch_size)
         return obs, rewards, terminals, truncations
 
     def _log(self, deferred: bool = False):
@@ -1189,7 +1228,7 @@ class VecEnv:
     def load_state(self, env: int, state: bytes):
         """Install a v9 savestate into one env (pk_load_env; pyboy_binding.py:59-69)."""
         self.emu.load_env(self.phys(env), state)
-        if self.frame_stack or self.probes is not None:
+        if self.frame_stack or self.probes is not None or self.tile_view:
             self._join_streams()
             m = torch.zeros(self.emu.n, dtype=torch.uint8, device=self.device)
             m[self.phys(env)] = 1
@@ -1203,6 +1242,18 @@ class VecEnv:
             raise RuntimeError("VecEnv(probes=..., probe_features=True) keeps the probe values")
         self._join_streams()
         return self._logical(self._probe_feat).clone()
+
+    def tile_obs(self) -> torch.Tensor:
+        """The tile view, int16 (P, 18, 20) per env, -1 = nothing; needs tile_view=.  Between a recv() and
+        its send() of the sub-batch pipeline: the rows of the sub-batch recv() returned, a view of the
+        emulator's buffer that the sub-batch's next step overwrites (no copy, no wait beyond recv()'s).
+        Otherwise every env's rows in env order, after a pipeline join."""
+        if not self.tile_view:
+            raise RuntimeError('VecEnv(tile_view="id" or "hash") keeps the tile view')
+        if self.num_batches > 1 and self._current is not None:
+            return self.emu.tiles[self._prange(self._current)]
+        self._join_streams()
+        return self._logical(self.emu.tiles)
 
     def video_recorder(self, envs, capacity: int = 1024):
         """A FrameRecorder (pokegym_amd/video.py) of the given envs' screens: call .capture() after

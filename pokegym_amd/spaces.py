@@ -72,3 +72,11 @@ def probe_space(m: int):
     if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 1 <= m <= 64:
         raise ValueError("a probe program has 1..64 probes")
     return Box(low=0, high=(1 << 30) - 1, shape=(int(m),), dtype=np.int32)
+
+
+def tile_space(planes: int):
+    """The tile view (VecEnv.tile_obs): int16 (planes, 18, 20), planes 1 or 2; -1 is "nothing", ids run to
+    383 and hashes to 2**15 - 1."""
+    if isinstance(planes, bool) or planes not in (1, 2):
+        raise ValueError("a tile view has 1 or 2 planes")
+    return Box(low=-1, high=(1 << 15) - 1, shape=(int(planes), 18, 20), dtype=np.int16)
