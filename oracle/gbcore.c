@@ -761,27 +761,42 @@ static uint32_t cpu_tick(gb_t* gb) {
  * PK_FRAME_BUDGET units (cycles + 1 per tick) the frame is ended.  The HIP kernel does the same. */
 #define PK_FRAME_BUDGET (16u * FRAME_CYCLES)
 
+/* one pass of the frame loop's body: cpu.tick, HALT fast-forward, timer, LCD; returns its cycles */
+static inline uint64_t gb_iterate(gb_t* gb) {
+    uint64_t cycles = cpu_tick(gb);
+    if (gb->halted) {
+        /* HALT fast-forward: max(0, min(lcd, timer)) cycles */
+        int64_t a = lcd_cycles_to_interrupt(gb), b = timer_cycles_to_interrupt(gb);
+        int64_t m = a < b ? a : b;
+        cycles = m < 0 ? 0 : (uint64_t)m;
+    }
+    if (timer_tick(gb, (uint32_t)cycles)) gb->IF |= INTR_TIMER;
+    gb->IF |= lcd_tick(gb, (uint32_t)cycles);
+    gb->iter_count++;
+    gb->cyc_total += cycles;
+    if (gb->halted) gb->cyc_halted += cycles;
+    if (!(gb->LCDC & 0x80)) gb->cyc_lcdoff += cycles;
+    return cycles;
+}
+
 void gb_tick(gb_t* gb) {
     uint32_t budget = 0;
     do {
-        uint64_t cycles = cpu_tick(gb);
-        if (gb->halted) {
-            /* HALT fast-forward: max(0, min(lcd, timer)) cycles */
-            int64_t a = lcd_cycles_to_interrupt(gb), b = timer_cycles_to_interrupt(gb);
-            int64_t m = a < b ? a : b;
-            cycles = m < 0 ? 0 : (uint64_t)m;
-        }
-        if (timer_tick(gb, (uint32_t)cycles)) gb->IF |= INTR_TIMER;
-        gb->IF |= lcd_tick(gb, (uint32_t)cycles);
-        budget += (uint32_t)cycles + 1u;
-        gb->iter_count++;
-        gb->cyc_total += cycles;
-        if (gb->halted) gb->cyc_halted += cycles;
-        if (!(gb->LCDC & 0x80)) gb->cyc_lcdoff += cycles;
+        budget += (uint32_t)gb_iterate(gb) + 1u;
         if (budget > PK_FRAME_BUDGET) gb->frame_done = 1;
     } while (!gb->frame_done);
     gb->frame_done = 0;
     gb->frame_count++;
+}
+
+/* n passes of gb_tick's loop body without the frame loop: stops anywhere, mid-frame included, so
+ * that gb_save_state gives a state with a consistent LCD phase there (tests/state_cases.py).  A
+ * frame end inside the passes is passed over (no frame is counted, no watchdog budget kept). */
+void gb_run_instrs(gb_t* gb, uint32_t n) {
+    for (uint32_t i = 0; i < n; i++) {
+        (void)gb_iterate(gb);
+        gb->frame_done = 0;
+    }
 }
 
 void gb_set_rendering(gb_t* gb, int on) { gb->render = on ? 1 : 0; }

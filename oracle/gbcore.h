@@ -55,6 +55,8 @@ void gb_button(gb_t* gb, int button, int pressed);
 void gb_set_rendering(gb_t* gb, int on);
 /* one PyBoy frame (Motherboard.tick) */
 void gb_tick(gb_t* gb);
+/* n passes of gb_tick's loop body (one cpu.tick each) without the frame loop: stops mid-frame */
+void gb_run_instrs(gb_t* gb, uint32_t n);
 /* pyboy_binding.run_action_on_emulator: action id per ACTIONS (pyboy_binding.py:40) */
 void gb_run_action(gb_t* gb, int action, int frame_skip, int release_frame);
 /* action -> button: 0 Down 1 Left 2 Right 3 Up 4 A 5 B 6 Start 7 Select; 8 = no press (extension) */

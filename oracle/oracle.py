@@ -44,6 +44,7 @@ def lib():
         L.gb_button.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
         L.gb_set_rendering.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.gb_tick.argtypes = [ctypes.c_void_p]
+        L.gb_run_instrs.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
         L.gb_run_action.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int]
         L.gb_read.restype = ctypes.c_uint8
         L.gb_read.argtypes = [ctypes.c_void_p, ctypes.c_uint16]
@@ -119,6 +120,10 @@ class GB:
 
     def tick(self):
         lib().gb_tick(self.h)
+
+    def run_instrs(self, n: int):
+        """n passes of the frame loop's body (gb_run_instrs): stops anywhere, mid-frame included."""
+        lib().gb_run_instrs(self.h, int(n))
 
     def button(self, b: int, pressed: bool):
         lib().gb_button(self.h, b, 1 if pressed else 0)

@@ -1215,6 +1215,11 @@ __global__ void __launch_bounds__(PK_K1_MAX_THREADS) PK_K1_KERNEL(PkStepArgs A) 
             e3 = ucv[di * 4u + 3u];
             PK_STAMP_AT(9);
         }
+        // an instruction that runs with `queued` set while an interrupt is pending is followed by the
+        // interrupt check (it clears queued): nothing may fuse onto it — no bytes for a pair.  Keyed
+        // on queued and pending whatever IME is: without IME the check dispatches nothing and the
+        // pair would compute the same, so the plain rule is kept instead of a third condition
+        pav = sel((cpu0 & (CPU_QUEUED | CPU_PEND)) == (CPU_QUEUED | CPU_PEND), 0u, pav);
         // ---------------- block copy and LY poll (pk_copy_loop, pk_poll_loop) ----------------
         // whole passes of the loop run here; the iteration then executes the next pass's first
         // instruction as usual (the loop's first bytes identify it: no INT pseudo-op has them)

@@ -135,7 +135,25 @@ extern "C" void pk_sim_census_get(uint32_t* out /* 4 * 65536 */) {
     std::lock_guard<std::mutex> l(g_trace_mu);
     for (size_t i = 0; g_census && i < 4 * 65536; i++) out[i] = g_census[i].load();
 }
+// per-env summary over every env (tests/state_common.py), PK_SUM words per env: passes skipped by
+// each loop fast path ([0] copy, [1] poll, [2] dec: the skip record's loop length 7 / 3 / 2), the OR
+// of the iterations' event bits ([3]), the first iteration's ([4]), the iterations so far ([5]), and
+// the loops that skipped in the env's first iteration ([6]: bit 0 copy, 1 poll, 2 dec).  One env is
+// stepped by one thread, so a row needs no lock; enable and get only between steps (no kernel
+// running): enable reallocates the rows the kernel threads index.
+#define PK_SUM 8u
+static std::vector<uint32_t> g_sum;
+extern "C" void pk_sim_summary_enable(uint32_t n_envs) { g_sum.assign((size_t)n_envs * PK_SUM, 0u); }
+extern "C" void pk_sim_summary_get(uint32_t* out, uint64_t words) {
+    memcpy(out, g_sum.data(), (words < g_sum.size() ? words : g_sum.size()) * 4);
+}
 extern "C" void pk_sim_trace(uint32_t env, uint32_t pc, uint32_t w0, uint32_t w1, uint32_t sp, uint32_t op) {
+    if ((op & 0x1000u) && ((size_t)env + 1u) * PK_SUM <= g_sum.size()) {
+        const uint32_t len = op & 0xFFFu, k = len == 7u ? 0u : len == 3u ? 1u : 2u;
+        uint32_t* q = &g_sum[(size_t)env * PK_SUM];
+        q[k] += w0;
+        if (!q[5]) q[6] |= 1u << k;   // the skip record comes before its iteration's PK_ITER
+    }
     if (g_census && !(op & 0x1000u)) {
         const size_t i = ((op >> 13) & 1u) * 65536u + (pc & 0xFFFFu);
         g_census[i].fetch_add(1u);
@@ -165,6 +183,11 @@ extern "C" void pk_sim_iter_enable(uint32_t n_envs, int on) {
     g_iter_on = on != 0;
 }
 extern "C" void pk_sim_iter(uint32_t env, uint32_t ev) {
+    if (((size_t)env + 1u) * PK_SUM <= g_sum.size()) {
+        uint32_t* q = &g_sum[(size_t)env * PK_SUM];
+        q[3] |= ev;
+        if (!q[5]++) q[4] = ev;
+    }
     if (!g_iter_on || env >= g_iter.size()) return;
     g_iter[env].push_back(ev);   // one env is stepped by one thread: no lock needed
 }
